@@ -2,8 +2,18 @@
 """Headline benchmark: bench_4-style distributed exact k-NN classification on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--strategy farm] ...
+    python bench.py --gpus 1 --steps K --warmup W --full              # + everything beside it
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR  # + the last step's results
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed
+steps, the result line.  --full adds what the benchmark measures beside the headline, after the
+timed steps: the untimed traced steps (per_rank rows, collective_check), the RCCL all-reduce bus
+bandwidth, the large-N shapes (large_n) and the reference-contract processes
+(reference_contract*).  --dump-outputs DIR writes what the last timed step returned (labels,
+checksums, report bytes) as DIR/<name>.npy: the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Metric (BASELINE.json): "samples/sec (whole node) on bench_4" = classified queries per second
 over all GPUs.  One step = one full Engine::KNN call exactly as the reference times it
@@ -26,9 +36,10 @@ Ranks: `python bench.py --gpus N` with N > 1 and no torchrun environment launche
 their exit code; it refuses to run when fewer than N GPUs are visible, unless DMLP_DATA_PLANE=host
 (the one-GPU rehearsal: N ranks share the GPU over the host-staged gloo plane).  Under torchrun,
 --gpus must equal WORLD_SIZE.  Rank 0's JSON then carries the world the process group really had
-(rccl_world / data_plane), an RCCL all-reduce check and its bus bandwidth, and per rank: ms/step,
-NUMA node, phase times and PCIe / collective bytes from an untimed traced pass after the timed
-steps, plus a rank-by-rank comparison of the collective sequence (parallel/dist_api.py).
+(rccl_world / data_plane) and an RCCL all-reduce check; with --full also its bus bandwidth, and
+per rank: ms/step, NUMA node, phase times and PCIe / collective bytes from an untimed traced pass
+after the timed steps, plus a rank-by-rank comparison of the collective sequence
+(parallel/dist_api.py).
 """
 from __future__ import annotations
 
@@ -105,13 +116,25 @@ def main(argv=None):
     ap.add_argument("--verify", action="store_true",
                     help="compare a SHA-256 digest of the WHOLE rank-0 report (every query line) "
                          "with the CPU oracle's (C++ fp64 brute force, outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the benchmark measures beside the "
+                         "headline: the traced steps (--diag-steps), the all-reduce bus bandwidth "
+                         "(unless --no-busbw), the large-N shapes (unless DMLP_BENCH_LARGE_N=0) and "
+                         "the reference-contract processes (--contract-runs); a run without --full "
+                         "does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned on rank 0 "
+                         "as DIR/<name>.npy: label (float32 [Q]), checksum (float64 [Q, 2]: high "
+                         "and low 32 bits) and report (float32: the report text's bytes); an "
+                         "array above its share of 64 MB is written as a fixed seeded sample")
     ap.add_argument("--no-busbw", action="store_true")
     ap.add_argument("--diag-steps", type=int, default=3,
-                    help="untimed traced steps after the timed ones: per-rank phase times, PCIe "
-                         "and collective bytes, collective-sequence check (0: skip)")
+                    help="--full: untimed traced steps after the timed ones: per-rank phase times, "
+                         "PCIe and collective bytes, collective-sequence check (0: skip)")
     ap.add_argument("--contract-runs", type=int,
                     default=int(os.environ.get("DMLP_BENCH_CONTRACT_RUNS", "3")),
-                    help="one GPU: after the timed steps, this many fresh processes of the engine.h "
+                    help="--full, "
+                         "one GPU: after the timed steps, this many fresh processes of the engine.h "
                          "drop-in linked with the reference's own common.cpp at this config (the "
                          "reference's contract: one Engine::KNN call per process, parse untimed, "
                          "the report written to a redirected stdout) -> reference_contract in the "
@@ -121,6 +144,9 @@ def main(argv=None):
                          "'Time taken' = KNN + report + barrier, common.cpp:121-131) at this "
                          "config AND at BASELINE.md's Q = 1000, one process per run")
     a = ap.parse_args(argv)
+    if a.dump_outputs and (a.steps < 1 or a.harness != "python"):
+        ap.error("--dump-outputs writes the last timed step's results: it needs --steps >= 1 "
+                 "and the python harness")
     if a.harness in ("native", "dropin"):
         return _bench_native(a)
     rc = _launch_ranks(a, argv)
@@ -167,8 +193,10 @@ def main(argv=None):
             setattr(inp, name + "_t", torch.from_numpy(getattr(inp, name)).pin_memory())
     eng = Engine(a.strategy, comm=comm, exact=a.exact, schedule=a.schedule)
 
+    last = [None]  # the last step's KNNOutput (rank 0), for --dump-outputs
+
     def step():
-        out = eng.KNN(inp.params if comm.is_root else None, inp, None)
+        out = last[0] = eng.KNN(inp.params if comm.is_root else None, inp, None)
         return eng.report(out) if out is not None else None
 
     import torch as _t
@@ -207,6 +235,9 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     thr1 = _cgroup_cpu_stat()
     steps_native = K.step_stats()  # this rank's timed steps served by the native step
+    if a.dump_outputs and comm.is_root:
+        # before anything else runs a step: the report is a view into a reused host buffer
+        _dump_outputs(a.dump_outputs, last[0], rep)
     elapsed_mine = elapsed
     # max over ranks
     el = torch.tensor([elapsed], dtype=torch.float64, device=comm.device)
@@ -247,9 +278,9 @@ def main(argv=None):
             "usage_ms": round((thr1.get("usage_usec", 0) - thr0.get("usage_usec", 0)) / 1e3, 1),
             "nr_throttled": thr1.get("nr_throttled", 0) - thr0.get("nr_throttled", 0),
             "throttled_ms": round((thr1.get("throttled_usec", 0) - thr0.get("throttled_usec", 0)) / 1e3, 1)}
-    if a.diag_steps > 0:
+    if a.full and a.diag_steps > 0:
         extra.update(_diagnostics(comm, eng, step, a.diag_steps, my_ms, steps_native))
-    if world > 1 and comm.backend == "nccl" and not a.no_busbw:
+    if a.full and world > 1 and comm.backend == "nccl" and not a.no_busbw:
         # a diagnostic beside the headline: a failure records itself instead of losing the line
         try:
             extra["allreduce_busbw_GBps"] = round(_allreduce_busbw(comm), 1)
@@ -270,7 +301,7 @@ def main(argv=None):
         extra["verify_ok"] = got == ref
         extra["verify_s"] = round(time.perf_counter() - t_v, 1)
 
-    if (world == 1 and comm.on_gpu and not a.exact
+    if (a.full and world == 1 and comm.on_gpu and not a.exact
             and os.environ.get("DMLP_BENCH_LARGE_N", "1") != "0"):
         # the large-N regime beside the headline (after its timed steps; a failure records itself)
         try:
@@ -278,7 +309,7 @@ def main(argv=None):
         except Exception as e:  # noqa: BLE001
             extra["large_n"] = {"error": f"{type(e).__name__}: {e}"[-300:]}
 
-    if a.contract_runs > 0 and comm.on_gpu:
+    if a.full and a.contract_runs > 0 and comm.on_gpu:
         # the same config through the reference's own contract (bench_4's binary is timed this
         # way by run_bench.sh:114-120): fresh processes, median of their Engine::KNN clocks.  One
         # GPU: the drop-in run directly with stdout to a file, and as run_bench.sh:84 launches it
@@ -338,6 +369,28 @@ def main(argv=None):
         inp.close()
     eng.close()
     return 0
+
+
+def _dump_outputs(path, out, rep):
+    """--dump-outputs: what the last timed step gave its caller on rank 0, one .npy per array —
+    label float32 [Q], checksum float64 [Q, 2] (the uint64's high and low 32 bits, each exact in
+    a double) and report float32 [bytes] (the report text, one value per byte).  Each array has
+    a share of the 64 MB the directory may hold (8 + 16 + 32 MB); one above its share is written
+    as the rows a fixed seed picks (sorted, the same for equal lengths), so runs stay comparable."""
+    import numpy as np
+    cs = out.checksums_np()
+    arrays = {
+        "label": (out.labels_np().astype(np.float32), 8 << 20),
+        "checksum": (np.stack([cs >> np.uint64(32), cs & np.uint64(0xFFFFFFFF)],
+                              axis=1).astype(np.float64), 16 << 20),
+        "report": (np.frombuffer(bytes(rep), np.uint8).astype(np.float32), 32 << 20),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, (arr, cap) in arrays.items():
+        rows = cap // max(1, arr[:1].nbytes)
+        if len(arr) > rows:
+            arr = arr[np.sort(np.random.default_rng(0).choice(len(arr), rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def _large_n(a, shapes=((1_000_000, 32), (1_000_000, 128)), q=16384, warmup=2, steps=5):

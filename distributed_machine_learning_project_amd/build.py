@@ -252,12 +252,18 @@ REF_HARNESS = Path(os.environ.get("DMLP_REF_HARNESS", "/root/reference"))
 REF_STAGE = PKG / "_refharness"  # git-ignored, NOT gpurun-ignored (unlike _build/)
 
 
+def _readable(p: Path) -> bool:
+    """p is a file this user can read (a tree that exists but is closed to this user counts as
+    absent, where Path.exists() would raise)."""
+    return os.access(p, os.R_OK)
+
+
 def reference_harness() -> Path | None:
     """The reference's common.cpp to build the drop-in against: the reference tree when this
     machine has it, else the untracked copy build() staged in _refharness (it travels with
     the working tree to GPU boxes, which have no reference tree; it is never committed)."""
     for d in (REF_HARNESS, REF_STAGE):
-        if (d / "common.cpp").exists() and (d / "common.h").exists():
+        if _readable(d / "common.cpp") and _readable(d / "common.h"):
             return d / "common.cpp"
     return None
 
@@ -266,11 +272,11 @@ def stage_reference_harness() -> Path | None:
     """Copy the reference harness files (common.cpp, common.h, engine.h) into _refharness
     (git-ignored) so drop-in tests and `bench.py --harness dropin` can build against the
     reference's unmodified harness on a machine without the reference tree."""
-    if not (REF_HARNESS / "common.cpp").exists():
+    if not _readable(REF_HARNESS / "common.cpp"):
         return None
     REF_STAGE.mkdir(parents=True, exist_ok=True)
     for f in ("common.cpp", "common.h", "engine.h"):
-        if (REF_HARNESS / f).exists():
+        if _readable(REF_HARNESS / f):
             # copy + atomic rename: concurrent builders (pytest -n workers) never see a
             # half-written or missing file
             tmp = REF_STAGE / f"{f}.{os.getpid()}.tmp"

@@ -46,21 +46,14 @@ def test_k_equals_n(method):
 
 
 def test_generate_text_matches_reference_generator():
-    """Byte-identical to the reference's generate_input.py for the same arguments and seed."""
+    """Byte-identical to the reference's generate_input.py for the same arguments and seed:
+    tests/golden/generate_input_seed11.txt is what it wrote for --num_data 50 --num_queries 7
+    --num_attrs 3 --min -5 --max 5 --minK 1 --maxK 9 --num_labels 4 --seed 11."""
     import os
-    import subprocess
-    import sys
-    import tempfile
-    refgen = "/root/reference/generate_input.py"
-    if not os.path.exists(refgen):
-        pytest.skip("reference not mounted")
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "in.txt")
-        subprocess.run([sys.executable, refgen, "--num_data", "50", "--num_queries", "7",
-                        "--num_attrs", "3", "--min", "-5", "--max", "5", "--minK", "1",
-                        "--maxK", "9", "--num_labels", "4", "--output", out, "--seed", "11"],
-                       check=True, capture_output=True)
-        ref_txt = open(out).read()
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                          "generate_input_seed11.txt")
+    with open(golden, newline="") as f:
+        ref_txt = f.read()
     assert dmlp.generate_text(50, 7, 3, -5, 5, 1, 9, 4, seed=11) == ref_txt
 
 

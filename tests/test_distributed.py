@@ -277,7 +277,8 @@ def test_bench_launches_its_ranks(ingress):
     verify against the oracle."""
     import json
     r = _bench(["--gpus", "3", "--steps", "2", "--warmup", "1", "--min-warmup-s", "0",
-                "--n-data", "1500", "--q-per-gpu", "200", "--verify", "--ingress", ingress],
+                "--n-data", "1500", "--q-per-gpu", "200", "--verify", "--ingress", ingress,
+                "--full"],
                {"DMLP_DATA_PLANE": "host"})
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -317,7 +318,8 @@ def test_bench_survives_diagnostics_failure():
     skipped, and rank 0 prints a valid, verified line (np 3)."""
     import json
     r = _bench(["--gpus", "3", "--steps", "2", "--warmup", "1", "--min-warmup-s", "0",
-                "--n-data", "1500", "--q-per-gpu", "200", "--verify", "--diag-steps", "1"],
+                "--n-data", "1500", "--q-per-gpu", "200", "--verify", "--diag-steps", "1",
+                "--full"],
                {"DMLP_DATA_PLANE": "host", "DMLP_DIAG_FAIL": "1"})
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -325,6 +327,43 @@ def test_bench_survives_diagnostics_failure():
     rows = res["per_rank"]
     assert "error" in rows[1] and "error" not in rows[0] and "error" not in rows[2]
     assert "collective_check" not in res
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A run without --full prints the headline line and none of what --full adds (no traced
+    steps, no large-N shapes, no reference-contract runs); --dump-outputs writes the last timed
+    step's labels, checksums and report as float .npy files that agree with each other and with
+    the exact CPU path, identical from run to run."""
+    import json
+    import distributed_machine_learning_project_amd as dmlp
+    from distributed_machine_learning_project_amd.ops import knn as K
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--min-warmup-s", "0",
+                    "--n-data", "1500", "--q-per-gpu", "200", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        res = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["dtype"] == "fp64" and res["higher_is_better"] is True
+        for key in ("per_rank", "diag_steps", "large_n", "reference_contract",
+                    "reference_contract_mpiexec", "allreduce_busbw_GBps"):
+            assert key not in res, key
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == [
+            "checksum.npy", "label.npy", "report.npy"]
+        dumps.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("label", "checksum", "report")})
+    a, b = dumps
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    assert a["label"].dtype == np.float32 and a["label"].shape == (200,)
+    assert a["checksum"].dtype == np.float64 and a["checksum"].shape == (200, 2)
+    assert a["report"].dtype == np.float32
+    cs = (a["checksum"][:, 0].astype(np.uint64) << np.uint64(32)) | a["checksum"][:, 1].astype(np.uint64)
+    assert a["report"].astype(np.uint8).tobytes() == dmlp.format_report(cs)
+    inp = dmlp.generate(1500, 200, 32, 0.0, 1000.0, 16, 16, 10, seed=42)  # bench.py's input
+    _, i_ref = K.knn_cpu(inp.X, inp.Qx, inp.k)
+    lab_ref, cs_ref = K.finalize_cpu(i_ref, inp.k, inp.labels)
+    assert np.array_equal(cs, np.asarray(cs_ref).view(np.uint64))
+    assert np.array_equal(a["label"], np.asarray(lab_ref).astype(np.float32))
 
 
 def test_collective_log_compare():

@@ -209,7 +209,7 @@ def test_bench_self_launch_rehearsal(np_):
     env = dict(os.environ, DMLP_DATA_PLANE="host", OMP_NUM_THREADS="2")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(np_), "--steps", "3",
            "--warmup", "1", "--min-warmup-s", "0", "--n-data", "20000", "--q-per-gpu", "2048",
-           "--verify", "--ingress", "root", "--no-busbw"]
+           "--verify", "--ingress", "root", "--no-busbw", "--full"]
     r = subprocess.run(cmd, capture_output=True, env=env, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -230,7 +230,7 @@ def test_bench_driver_path_eight_ranks():
                DMLP_BENCH_CONTRACT_RUNS="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3",
            "--warmup", "1", "--min-warmup-s", "0", "--n-data", "20000", "--q-per-gpu", "2048",
-           "--verify", "--no-busbw"]
+           "--verify", "--no-busbw", "--full"]
     r = subprocess.run(cmd, capture_output=True, env=env, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads(r.stdout.decode().strip().splitlines()[-1])

@@ -7,7 +7,7 @@
 # tasks:
 #   tests      pytest -m gpu (the round-end GPU tier)
 #   ktests     the GPU tests selected by KTESTS (a pytest -k expression)
-#   bench      python bench.py (defaults: 1 GPU, headline config)
+#   bench      python bench.py --full (defaults: 1 GPU, headline config, everything beside it)
 #   verify     python bench.py --verify (every report line vs the exact CPU path)
 #   prof       rocprofv3 --kernel-trace --stats over a short bench run (kernel split)
 #   timeline   rocprofv3 kernel + memory-copy trace of the last steps (tools/timeline.py)
@@ -51,8 +51,8 @@ cd "${GRAFT_REPO_ROOT:-.}"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-# bench.py's reference-contract runs (fresh drop-in processes after the timed steps) only where a
-# task wants the driver's line: bench, bench3, final
+# bench.py --full's reference-contract runs (fresh drop-in processes after the timed steps) and
+# large-N shapes only where a task wants the driver's line: bench, bench3, final
 export DMLP_BENCH_CONTRACT_RUNS=0 DMLP_BENCH_LARGE_N=0
 step() {  # name seconds cmd...  (stdout+stderr to $OUT/name.log)
   local name=$1 secs=$2
@@ -72,9 +72,9 @@ for task in "$@"; do
       step ktests 600 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 120 \
           --timeout-method thread -k "${KTESTS:?KTESTS}" ;;
     bench)
-      DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench 300 python bench.py ;;
+      DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench 300 python bench.py --full ;;
     bench3)  # three headline runs in a row (run-to-run spread: timed_step_ms, cgroup throttling)
-      for r in 1 2 3; do DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench_$r 300 python bench.py; done ;;
+      for r in 1 2 3; do DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench_$r 300 python bench.py --full; done ;;
     verify)
       step verify 300 python bench.py --steps 20 --warmup 2 --verify ;;
     exact)
@@ -178,7 +178,7 @@ for task in "$@"; do
         Qp=$([ $P = 3 ] && echo 65536 || echo 16384)
         for pl in 1 0; do
           DMLP_DATA_PLANE=host KNN_PLANE=$pl step plane_p${P}_$pl 400 python bench.py --gpus $P \
-              --steps 10 --warmup 2 --min-warmup-s 1 --q-per-gpu $Qp --verify --no-busbw
+              --steps 10 --warmup 2 --min-warmup-s 1 --q-per-gpu $Qp --verify --no-busbw --full
         done
       done ;;
     rehearsal)  # host budget of an 8-GPU node: the GPU rank + 7 CPU phantom ranks, 2 threads each
@@ -209,7 +209,7 @@ for task in "$@"; do
       for P in 3 4; do
         for M in h2d xgmi; do
           DMLP_DATA_PLANE=host KNN_DATA_INGRESS=$M step modes_p${P}_$M 400 python bench.py --gpus $P \
-              --steps 10 --warmup 2 --min-warmup-s 1 --q-per-gpu 32768 --verify --no-busbw
+              --steps 10 --warmup 2 --min-warmup-s 1 --q-per-gpu 32768 --verify --no-busbw --full
         done
       done
       grep -ho '"ms_per_step": [0-9.]*\|"verify_ok": [a-z]*\|"collective_bytes_per_step": {[^}]*}' \
@@ -353,7 +353,7 @@ for task in "$@"; do
     p3c)  # the P = 3 host-plane rehearsal with the node contract after the timed steps (rank 0
           # runs the drop-in through mpiexec -n 3, the other ranks wait on the segment)
       DMLP_BENCH_CONTRACT_RUNS=2 KNN_DATA_PLANE=host DMLP_DATA_PLANE=host step p3c 600 python bench.py \
-          --gpus 3 --steps 20 --warmup 2 --min-warmup-s 1 --no-busbw
+          --gpus 3 --steps 20 --warmup 2 --min-warmup-s 1 --no-busbw --full
       grep -o '"reference_contract_node": {[^}]*' "$OUT/p3c.log" | head -c 600; echo ;;
     k200)  # the two-pass class (k = 200) at N = 1e7: device vs host render, alternating
       for R in 1 2; do
@@ -429,7 +429,7 @@ for task in "$@"; do
       step tests 1000 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 120 \
           --timeout-method thread
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-      DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5
+      DMLP_BENCH_CONTRACT_RUNS=3 DMLP_BENCH_LARGE_N=1 step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full
       step verify 300 python bench.py --steps 200 --verify
       step exact 300 python bench.py --exact --steps 5 --warmup 1 --min-warmup-s 0 --verify
       DMLP_DATA_PLANE=host step p3 400 python bench.py --gpus 3 --steps 30 --warmup 3 \

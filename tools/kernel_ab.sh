@@ -7,7 +7,8 @@
 #   AB_PROF=0 AB_ROUNDS=3 gpurun -- bash tools/kernel_ab.sh c1:DMLP_HOST_OPS_CHUNKS=1 c2:DMLP_HOST_OPS_CHUNKS=2
 # AB_ARGS: extra bench.py arguments (e.g. "--q-per-gpu 32768").
 # AB_PROF=1 (default): rocprofv3 --kernel-trace --stats per run (tools/ab_summary.py reads the
-# kernel medians); AB_PROF=0: plain bench.py runs (host-side settings: no tracer overhead).
+# kernel medians); AB_PROF=0: bench.py --full runs without a profiler (host-side settings: no
+# tracer overhead; tools/ab_timeline.py reads their per_rank step timelines).
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 export DMLP_BENCH_CONTRACT_RUNS=0  # no reference-contract processes after the timed steps
@@ -28,7 +29,7 @@ for round in $(seq 1 "$ROUNDS"); do
     fi
     LOG=gpurun_out/ab/$NAME.$round.log
     if [ "$PROF" = 0 ]; then
-      env "${ENVS[@]}" timeout -k 10 120 python bench.py --steps "$STEPS" --warmup 20 --no-busbw \
+      env "${ENVS[@]}" timeout -k 10 120 python bench.py --steps "$STEPS" --warmup 20 --no-busbw --full \
           ${AB_ARGS:-} > "$LOG" 2>&1 || { tail -20 "$LOG"; exit 1; }
     else
       env "${ENVS[@]}" timeout -k 10 180 rocprofv3 --kernel-trace --stats -d gpurun_out/ab/$NAME.$round \
