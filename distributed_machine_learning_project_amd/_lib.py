@@ -72,6 +72,12 @@ _SIGS = {
     "dmlp_screen_x1_early": (i32, [i32, i32, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, vp, vp,
                                    i32, i32, vp, vp, vp, vp, vp]),
     "dmlp_screen_x1_group_rows": (i32, [i32]),
+    "dmlp_screen_x1_group_rows_kt": (i32, [i32, i32]),
+    "dmlp_refine_groups_rm": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i64,
+                                    vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp,
+                                    vp, vp]),
+    "dmlp_refine_pair_path": (i32, [i32, i32, i32, i32, i32, i32]),
+    "dmlp_x1_rowmajor": (i32, [vp, i64, i32, vp, vp]),
     "dmlp_screen_x1_part": (i32, [i32, i32, i32, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, vp, vp,
                                   i32, i32, i32, vp, vp, vp, vp]),
     "dmlp_refine_groups": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),

@@ -218,7 +218,8 @@ int dmlp_refine_groups(int cap, const int* cand_ids, const int* cand_cnt, const 
                        int kstride, const int* labels, int label_lo, int label_hi,
                        int* out_label, uint64_t* out_cs, int* status, int* ovf_count, void* stream);
 // collect = 1: the lists of dmlp_screen_x1_collect (large k): k <= 256 over <= 512 filtered
-// members (fp16 host operands, hl = 1); collect = 0 is dmlp_refine_groups.
+// members (fp16 host operands, hl = 1); collect = 0 is dmlp_refine_groups: cap must be the
+// producing screen's dmlp_screen_x1_cap_kt(KT, kmax), which also tells the rows per group entry.
 int dmlp_refine_groups2(int cap, const int* cand_ids, const int* cand_cnt, const float* cand_h,
                         int S, const double* X, int A, const double* Qx, const void* xfrag,
                         const float* xinit, const void* qhi, int KT, int hl, int64_t n_points,

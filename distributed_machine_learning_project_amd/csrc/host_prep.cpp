@@ -8,7 +8,7 @@
 //
 // The host render is the fp16 single-term image (hl = 1 for dmlp_screen_x1 / dmlp_refine_groups):
 // c = q - mu in fp64; hi = fp16_rn(fp32_rn(c)) — 11 significant bits where bf16 has 8, so the
-// single-term error bound is 4x tighter and fewer groups reach the re-rank; |c| >= 65504 (the
+// single-term error bound is 8x tighter and fewer groups reach the re-rank; |c| >= 65504 (the
 // fp16 range) or NaN flags the input as outside the screen's range (the caller then takes the
 // device path, whose bf16 hi/lo image covers any finite data below 1e15).
 #include "dmlp.h"

@@ -1580,8 +1580,12 @@ extern "C" int dmlp_refine_groups2(int cap, const int* cand_ids, const int* cand
                                    int* out_i, int kstride, const int* labels, int label_lo,
                                    int label_hi, int* out_label, uint64_t* out_cs, int* status,
                                    int* ovf_count, int collect, void* stream) {
-  // (the lists' producer, by its cap: dmlp_screen_x1_cap(kmax) of the screen that wrote them)
-  const int grows = collect ? 4 : dmlp_screen_x1_group_rows_kt(KT, 64);
+  // rows per group entry as the producing screen wrote them, told by its cap: the 16-entry
+  // screen's id stride (dmlp_screen_x1_cap_kt(KT, 1)) means its groups, any other the 32-entry
+  // screen's; the COLLECT pass always writes 4-row groups
+  const int grows = collect ? 4
+                    : cap == dmlp_screen_x1_cap_kt(KT, 1) ? dmlp_screen_x1_group_rows_kt(KT, 1)
+                                                          : dmlp_screen_x1_group_rows_kt(KT, 64);
   return refine_groups_impl(cap, cand_ids, cand_cnt, cand_h, S, X, A, Qx, xfrag, nullptr, xinit,
                             qhi, KT, hl, n_points, qidx, qk, nq, out_d, out_i, kstride, labels,
                             label_lo, label_hi, out_label, out_cs, status, ovf_count, collect,

@@ -6,7 +6,7 @@
 //  * ONE bf16 product per attribute (hi(q') * hi(x')), not the 3-term split: a third of the MFMA
 //    work and half the fragment bytes.  The price is a wider error bound,
 //        |a - a_exact| <= r1 * |q'| * max|x'| + r2 * max|x'|^2,
-//    r1 ~ 2^-8 (bf16 rounding of both operands) — on the generate_input.py distribution that
+//    r1 ~ 2^-7 (bf16 rounding of both operands) — on the generate_input.py distribution that
 //    lets ~2x k candidates through instead of ~k, which the exact re-rank absorbs easily.
 //  * Candidate buffers hold 4-byte entries (top 16 bits of the fp32 4-row group max | 16-bit
 //    slice-relative group index), so a wave's 64 columns x 64 entries fit in 17 KiB of LDS and
@@ -19,7 +19,7 @@
 //
 // Element type: hl = 2 (prep.hip's device image) is bf16 hi/lo and runs v_mfma_f32_16x16x32_bf16;
 // hl = 1 (host_prep.cpp's hi-only image and query fragments) is fp16 and runs
-// v_mfma_f32_16x16x32_f16 at the same rate — 3 more significant bits per operand, a 4x tighter
+// v_mfma_f32_16x16x32_f16 at the same rate — 3 more significant bits per operand, an 8x tighter
 // bound r1 (plus r3, the absolute error of fp16 subnormals), so fewer groups reach the re-rank.
 //
 // Layout (mfma_f32_16x16x32_bf16): lane (c = lane & 15, kg = lane >> 4) of column tile ct holds
@@ -665,7 +665,8 @@ int launch_x1(int hl, const void* xfrag, const float* xinit, int64_t n_tiles, in
 }  // namespace
 
 // Screen error bound of the single-term form, per query q (fp32 score a = <q',x'> - |x'|^2/2):
-//   hi() = bf16(fp32(c)): |c - hi(c)| <= u|c|, u = 2^-9 (1 + 2^-15);  bf16 x bf16 products are
+//   hi() = bf16(fp32(c)): |c - hi(c)| <= u|c|, u = 2^-8 (1 + 2^-15) (8 significant bits: half a
+//   step of 2^-7 at c = 1, plus the fp32 rounding before it);  bf16 x bf16 products are
 //   exact in fp32; the MFMA chain rounds at most A + 1 partial sums, each bounded by
 //   sum|hi(q)hi(x)| + |x'|^2/2; xinit carries one fp32 rounding of |x'|^2/2.  With |x'| <= max:
 //     |a - a_exact| <= r1 |q'| max|x'| + r2 max|x'|^2,
@@ -680,7 +681,7 @@ int launch_x1(int hl, const void* xfrag, const float* xinit, int64_t n_tiles, in
 extern "C" void dmlp_screen_x1_bound2(int A, int hl, float* r1, float* r2, float* r3) {
   const bool f16 = hl == 1;
   const double u = f16 ? std::ldexp(1.0, -11) * (1.0 + std::ldexp(1.0, -12))
-                       : std::ldexp(1.0, -9) * (1.0 + std::ldexp(1.0, -15));
+                       : std::ldexp(1.0, -8) * (1.0 + std::ldexp(1.0, -15));
   const double e24 = std::ldexp(1.0, -24);
   *r1 = (float)(1.25 * (2.0 * u + u * u + (A + 2) * e24 * (1.0 + u) * (1.0 + u)));
   *r2 = (float)(1.25 * ((A + 2) * e24 * 0.5 + e24));
