@@ -22,12 +22,24 @@ extern "C" {
 // mu[A] = mean of the first min(N, 4096) rows (centering offset for the screen; any value is
 // correct, a good one only tightens the screen).
 int dmlp_center(const double* X, int64_t N, int A, double* mu, void* stream);
-// The exact path's fp64 MFMA screen (screen_f64.hip) + exact group re-rank: k <= 64, A <= 32,
-// results bit-identical to dmlp_exact_topk; overflowing queries get status[q] = 1 (nothing
-// written) and are counted into *ovf_count (device).  ws: dmlp_exact_f64_bytes bytes.
+// The exact path's fp64 MFMA screen (screen_f64.hip) + exact group re-rank: 1 <= k <= kmax <=
+// dmlp_exact_f64_kmax() (64), A <= dmlp_exact_f64_amax() (64), queries qidx[0..nq) (any order;
+// qk, status and the output rows are indexed by the row qidx[i]).  status[q] = 0: slots
+// [0, min(k_q, N)) hold the list, bit-identical to dmlp_exact_topk, and [min(k_q, N), kstride)
+// hold (+inf, -1).  status[q] = 1: the query is handed back (a slice's candidates overflowed,
+// more than 512 members survived the group threshold — pathological ties — or a magnitude is
+// past the fp32 key range): slots [0, k_q) stay untouched, [k_q, kstride) hold (+inf, -1), and
+// the caller runs dmlp_exact_topk on it.  *ovf_count (device) is ADDED the number of
+// handed-back queries, not set.  Rows that are not listed are untouched.  ws: exactly
+// dmlp_exact_f64_bytes(N, A, nq, kmax) bytes are used; fewer return -1 before any launch.
 int dmlp_exact_f64_amax(void);
 int dmlp_exact_f64_kmax(void);
 int64_t dmlp_exact_f64_bytes(int64_t N, int A, int nq, int kmax);
+// Where the screen's lists sit in ws (tests): out[8] = {S, tiles per slice, ids per (query,
+// slice) — 4 of which are slack: a slice keeps at most out[2] - 4 groups —, byte offsets of
+// cand_ids, cand_cnt, cand_h, the max-norm word, mu}.  An entry is key16 << 16 | slice-relative
+// index of a 4-row group, a count of -1 an overflowed slice.
+void dmlp_exact_f64_layout(int64_t N, int A, int nq, int kmax, int64_t* out);
 int dmlp_exact_f64(const double* X, int64_t N, int A, const double* Qx, const int* qidx,
                    const int* qk, int nq, int kmax, double* out_d, int* out_i, int kstride,
                    int* status, int* ovf_count, void* ws, int64_t ws_bytes, void* stream);
@@ -199,10 +211,14 @@ void dmlp_set_stream_sub(int sub);
 
 // ---------------------------------------------------------------- device: exact refine (K2 exact + K3 + K6)
 // Exact fp64 distances of the candidates, exact top-k under (dist asc, id desc).
-// Writes out_d/out_i[q*kstride + i], i < k_q (rest untouched).  status[q] = 1 if the query
-// overflowed and must take the exact fallback path, else 0 (and *ovf_count, if given, grows by
-// one per overflowed query: a running total).  Slots [k_q, kstride) get (+inf, -1).  If labels != NULL the vote and
-// checksum are fused (out_label[q], out_cs[q]); label_lo/label_hi give the label range.
+// Writes out_d/out_i[q*kstride + i], i < k_q ((+inf, -1) where fewer than k_q points exist).
+// Slots [k_q, kstride) of EVERY listed row get (+inf, -1), handed-back rows included: callers
+// need no fill pass.  status[q] = 1 if the query overflowed and must take the exact fallback
+// path (its slots [0, k_q) stay untouched), else 0 (and *ovf_count, if given, grows by one per
+// overflowed query: a running total).  If labels != NULL the vote and checksum are
+// fused (out_label[q], out_cs[q]).  label_lo / label_hi: every label lies in [label_lo,
+// label_hi), or label_hi <= label_lo when the range is not known (any labels; the vote then
+// counts instead of using its LDS histogram).  A given range must contain every label.
 int dmlp_refine(int cap, const int* cand_ids, const int* cand_cnt, int S, const double* X,
                 int A, const double* Qx, const int* qidx, const int* qk, int nq, double* out_d,
                 int* out_i, int kstride, const int* labels, int label_lo, int label_hi,
@@ -384,12 +400,20 @@ int dmlp_pipeline_set(const char* key, int value);
 void dmlp_pipeline_stats(int64_t* out);
 
 // ---------------------------------------------------------------- device: exact rows (K2, fallback)
-// D[i][n] = exact dist(Qx[qidx[i]], X[n]) for i < nq, n < N; ldd = row stride of D (>= N).
+// D[i][n] = exact dist(Qx[qidx[i]], X[n]) for i < nq, n < N; ldd = row stride of D (>= N; the
+// columns [N, ldd) stay untouched).
 int dmlp_exact_rows(const double* X, int64_t N, int A, const double* Qx, const int* qidx, int nq,
                     double* D, int64_t ldd, void* stream);
 
+// The exact entry points below (dmlp_fallback_topk, dmlp_fallback_select, dmlp_exact_topk) share
+// one output contract: for every listed row q = qidx[i] (any order) slots [0, min(k_q, N)) of
+// out_*[q * kstride ...] are written, sorted by (dist asc, id desc; a real neighbour at distance
+// +inf is a neighbour like any other); slots [min(k_q, N), kstride), rows that are not listed
+// and, in the workspace, every byte past the advertised size stay untouched.  Callers pre-fill
+// the padding.  A workspace smaller than advertised returns -3 before any launch.
+//
 // Exact top-k of the fallback queries qidx[0..nb): exact rows in descending-id order + stable
-// segmented radix sort; k from qk[qidx[i]] (clamped to N); nb*N < 2^31 (callers chunk).
+// segmented radix sort; k from qk[qidx[i]] (clamped to N); nb*N < 2^31 (callers chunk; -1).
 int64_t dmlp_fallback_bytes(int nb, int64_t N);
 int dmlp_fallback_topk(const double* X, int64_t N, int A, const double* Qx, const int* qidx,
                        const int* qk, int nb, void* ws, int64_t ws_bytes, double* out_d,
@@ -399,8 +423,8 @@ int dmlp_fallback_topk(const double* X, int64_t N, int A, const double* Qx, cons
 // exact distance bits + an LDS bitonic sort of the survivors (rows with larger k are skipped;
 // callers send those to dmlp_fallback_topk).  Workspace: dmlp_fallback_select_bytes(nb, N).
 int dmlp_fallback_select_kmax(void);
-// Fused streaming exact top-k (exact.hip), k <= dmlp_exact_topk_kmax(): no workspace, no
-// distance rows; kmax bounds the k of these queries.
+// Fused streaming exact top-k (exact.hip), k <= dmlp_exact_topk_kmax() (256): no workspace, no
+// distance rows; kmax bounds the k of these queries (kmax > 256 returns -1 before any launch).
 int dmlp_exact_topk_kmax(void);
 int dmlp_exact_topk_kmax_for(int64_t N);  // dispatch policy: fused vs rows + select
 int dmlp_exact_topk(const double* X, int64_t N, int A, const double* Qx, const int* qidx,
@@ -413,7 +437,11 @@ int dmlp_fallback_select(const double* X, int64_t N, int A, const double* Qx, co
 
 // ---------------------------------------------------------------- device: top-k merge (K4)
 // L sorted lists per query (list l of query q at in_*[l*list_stride + q*kin + j]), padded with
-// (+inf, -1).  Writes the merged top-k_q of every query q < nq to out_*[q*kout + i].
+// (+inf, -1); real entries may sit at distance +inf (id >= 0) and rank before the padding; only
+// the first min(k_q, kin) entries of a list are read.  Writes EVERY slot of out_*[q*kout + i],
+// i < kout, of every query q < nq, for every L in [1, 64]: the first min(k_q, kout) real entries
+// of the union under (dist asc, id desc), then (+inf, -1) — callers need no fill pass, and
+// nothing outside [0, nq * kout) is written.
 int dmlp_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,
                const int* qk, int nq, double* out_d, int* out_i, int kout, void* stream);
 

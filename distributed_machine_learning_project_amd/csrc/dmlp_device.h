@@ -180,8 +180,10 @@ __device__ __forceinline__ int wave_vote_by(const int* ids, int k, LabFn lab, in
                                             int label_hi, int* hist, int hist_cap) {
   const int lane = lane_id();
   long long best = -1;  // (count << 32) | (label ^ 0x80000000)
-  const int range = label_hi - label_lo;
-  if (range > 0 && range <= hist_cap) {
+  // 64-bit: a range that an int cannot hold (labels near INT_MIN / INT_MAX) takes the count path
+  const long long range64 = (long long)label_hi - (long long)label_lo;
+  if (range64 > 0 && range64 <= hist_cap) {
+    const int range = (int)range64;
     for (int i = lane; i < range; i += 64) hist[i] = 0;
     wave_sync();
     for (int i = lane; i < k; i += 64) {

@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <climits>
 #include <cstring>
 #include <thread>
 
@@ -256,7 +257,9 @@ class KnnCore {
       lo_ = 0; hi_ = 1;
       if (N_) {
         lo_ = *std::min_element(in->labels.begin(), in->labels.end());
-        hi_ = *std::max_element(in->labels.begin(), in->labels.end()) + 1;
+        const int lmax = *std::max_element(in->labels.begin(), in->labels.end());
+        if (lmax < INT_MAX) hi_ = lmax + 1;
+        else lo_ = hi_ = 0;  // no int holds lmax + 1: "not given", every vote counts
       }
       kmax_ = Q_ ? std::max(1, *std::max_element(in->k.begin(), in->k.end())) : 1;
     }

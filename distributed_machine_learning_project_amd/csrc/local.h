@@ -255,8 +255,9 @@ struct Local {
     CK(dmlp::dma_copy(qi, h, fq.size() * sizeof(int), st));
     base = 0;
     if (!fused.empty()) {
-      // A <= 32, 1 <= k <= 64: the fp64 MFMA screen + exact group re-rank (screen_f64.hip); its
-      // overflows (pathological ties) go to the fused VALU kernel.  DMLP_EXACT_F64=0: never.
+      // A <= 64 (dmlp_exact_f64_amax), 1 <= k <= 64: the fp64 MFMA screen + exact group re-rank
+      // (screen_f64.hip); its overflows (pathological ties) go to the fused VALU kernel.
+      // DMLP_EXACT_F64=0: never.
       int kfmin = kfmax;
       for (int q : fused) kfmin = std::min(kfmin, kk[q]);
       const bool f64 = !env_off("DMLP_EXACT_F64") && A <= dmlp_exact_f64_amax() && kfmin >= 1 &&

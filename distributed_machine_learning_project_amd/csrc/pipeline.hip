@@ -284,8 +284,10 @@ struct Step {
     if (a->labels && a->label_hi <= a->label_lo) {  // label range not given: the same
       int lmin = 0, lmax = -1;
       if (N > 0) dmlp_host_i32_range(a->labels, N, &lmin, &lmax);
-      a->label_lo = N > 0 ? lmin : 0;
-      a->label_hi = N > 0 ? lmax + 1 : 1;
+      // lmax == INT_MAX: [lo, lmax + 1) has no int form; (0, 0) makes every vote count instead
+      const bool fits = lmax < INT_MAX;
+      a->label_lo = N > 0 && fits ? lmin : 0;
+      a->label_hi = N > 0 ? (fits ? lmax + 1 : 0) : 1;
     }
     const int kst = a->kstride > 0 ? a->kstride : std::max(1, Q ? kmax : 1);
     if (Q > 0 && kmax > kst) return -3;

@@ -517,8 +517,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((GROUPS && 
 // rank in the union, i.e. its index in its own list plus, for every other list, the number of
 // entries ordered before it (a binary search over that list's real prefix; ties between lists
 // go to the lower list index).  The ranks of the real elements are therefore exactly
-// 0 .. total-1; each element with rank < k is stored once, and slots [total, k) get the
-// (+inf, -1) padding.  Padding entries (id < 0) form a suffix of each list.
+// 0 .. total-1; each element with rank < k is stored once, and slots [min(total, k), kout) get
+// the (+inf, -1) padding.  Padding entries (id < 0) form a suffix of each list.
 __global__ __launch_bounds__(256) void k_merge(const double* __restrict__ in_d,
                                                const int* __restrict__ in_i, int L,
                                                int64_t list_stride, int kin,
@@ -531,6 +531,7 @@ __global__ __launch_bounds__(256) void k_merge(const double* __restrict__ in_d,
   if (q >= nq) return;
   int k = qk[q];
   k = k < kout ? k : kout;
+  k = k > 0 ? k : 0;
   const int lim = k < kin ? k : kin;
   const int64_t qo = (int64_t)q * kin;
   int* cnt = s_cnt[wave];
@@ -575,7 +576,8 @@ __global__ __launch_bounds__(256) void k_merge(const double* __restrict__ in_d,
       out_i[(int64_t)q * kout + rank] = id;
     }
   }
-  for (int o = total + lane; o < k; o += 64) {
+  // every slot past the merged entries, up to kout, is padding (as in the L <= 8 kernels)
+  for (int o = (total < k ? total : k) + lane; o < kout; o += 64) {
     out_d[(int64_t)q * kout + o] = INFINITY;
     out_i[(int64_t)q * kout + o] = -1;
   }
@@ -602,6 +604,7 @@ __global__ __launch_bounds__(256) void k_merge_path(const double* __restrict__ i
   int (*s_cnt)[64] = s_cnt_all[wave];
   int k = qk[q];
   k = k < kout ? k : kout;
+  k = k > 0 ? k : 0;
   const int lim = k < kin ? k : kin;
   double* bd[2] = {(double*)smem, (double*)smem + (size_t)L * lcap};
   int* bi[2] = {(int*)((double*)smem + 2 * (size_t)L * lcap),
@@ -705,8 +708,8 @@ __global__ __launch_bounds__(256) void k_merge_path(const double* __restrict__ i
     cur ^= 1;
     Lc = Ln;
   }
-  const int total = s_cnt[cur][0];
-  for (int o = lane; o < k; o += 64) {
+  const int total = s_cnt[cur][0];  // <= k
+  for (int o = lane; o < kout; o += 64) {  // real entries, then padding up to kout
     const bool real = o < total;
     out_d[(int64_t)q * kout + o] = real ? bd[cur][o] : INFINITY;
     out_i[(int64_t)q * kout + o] = real ? bi[cur][o] : -1;

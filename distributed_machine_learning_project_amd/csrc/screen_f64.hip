@@ -500,8 +500,9 @@ extern "C" int64_t dmlp_exact_f64_bytes(int64_t N, int A, int nq, int kmax) {
 
 // Exact top-k of queries qidx[0..nq) (k <= 64, A <= 64): out_*[q * kstride + j], j < k, sorted by
 // (dist asc, id desc), bit-identical to dmlp_exact_topk.  A query whose candidates overflow gets
-// status[q] = 1 and nothing written (the caller runs dmlp_exact_topk on it); *ovf_count (device)
-// is ADDED the number of them.  ws: dmlp_exact_f64_bytes(N, A, nq, kmax) bytes.
+// status[q] = 1 and its slots [0, k) stay untouched (the caller runs dmlp_exact_topk on it);
+// *ovf_count (device) is ADDED the number of them.  Slots [k, kstride) of every listed row get
+// (+inf, -1) (dmlp.h).  ws: dmlp_exact_f64_bytes(N, A, nq, kmax) bytes.
 extern "C" int dmlp_exact_f64(const double* X, int64_t N, int A, const double* Qx, const int* qidx,
                               const int* qk, int nq, int kmax, double* out_d, int* out_i,
                               int kstride, int* status, int* ovf_count, void* ws, int64_t ws_bytes,

@@ -505,12 +505,9 @@ def merge_gpu(lists_d, lists_i, k_dev, kout: int):
     Ld = lists_d.contiguous()
     Li = lists_i.contiguous()
     Lc, Q, kin = Ld.shape
-    if Lc <= 8:  # the register merge writes every slot, padding included
-        out_d = torch.empty((Q, kout), dtype=torch.float64, device=Ld.device)
-        out_i = torch.empty((Q, kout), dtype=torch.int32, device=Ld.device)
-    else:
-        out_d = torch.full((Q, kout), float("inf"), dtype=torch.float64, device=Ld.device)
-        out_i = torch.full((Q, kout), -1, dtype=torch.int32, device=Ld.device)
+    # dmlp_merge writes every slot of [0, kout), padding included: no fill pass
+    out_d = torch.empty((Q, kout), dtype=torch.float64, device=Ld.device)
+    out_i = torch.empty((Q, kout), dtype=torch.int32, device=Ld.device)
     _lib.check(_lib.lib().dmlp_merge(_p(Ld), _p(Li), Lc, Q * kin, kin, _p(k_dev), Q, _p(out_d),
                                      _p(out_i), kout, _stream()), "merge")
     return out_d, out_i

@@ -54,6 +54,12 @@ def _root_arrays(be, inp):
             g("k", torch.int32))
 
 
+def _label_range(lmin: int, lmax: int):
+    """[lo, hi) of the labels as two C ints; a maximum of INT_MAX has no exclusive bound an int
+    holds: (0, 0), "not given", makes every vote count instead of using its histogram."""
+    return (lmin, lmax + 1) if lmax < 2 ** 31 - 1 else (0, 0)
+
+
 def _meta(comm, inp, with_shared=False):
     """Sizes, label range, kmax (engine.cpp:27-35) [+ whether the input is a node-shared
     segment that every rank has mapped].  With a node-shared segment (mapped by every rank by
@@ -63,7 +69,7 @@ def _meta(comm, inp, with_shared=False):
         N, A = inp.X.shape
         Q = inp.Qx.shape[0]
         lmin, lmax = _lib.i32_range(inp.labels)
-        lo, hi = (lmin, lmax + 1) if N else (0, 1)
+        lo, hi = _label_range(lmin, lmax) if N else (0, 1)
         kmin, kmx = _lib.i32_range(inp.k) if Q else (0, 0)
         kmax = max(1, kmx) if Q else 1
         inp.k_range_all = (kmin, kmx)  # this call's k bounds (the farm's world-1 dispatch)
@@ -75,7 +81,7 @@ def _meta(comm, inp, with_shared=False):
         # scanned inside every call, like the reference engines' own passes over the input
         from .. import _lib
         lmin, lmax = _lib.i32_range(inp.labels)
-        lo, hi = (lmin, lmax + 1) if N else (0, 1)
+        lo, hi = _label_range(lmin, lmax) if N else (0, 1)
         kmax = max(1, _lib.i32_range(inp.k)[1]) if Q else 1
         vals = [N, Q, A, lo, hi, kmax, int(bool(getattr(inp, "shared", False)))]
     else:
