@@ -129,6 +129,11 @@ _SIGS = {
     "dmlp_cpu_write_input": (i32, [C.c_char_p, vp, vp, i64, vp, vp, i64, i32]),
     "dmlp_cpu_i32_range": (None, [vp, i64, i32p, i32p]),
     "dmlp_host_i32_range": (None, [vp, i64, i32p, i32p]),
+    "dmlp_host_pool_begin": (i32, [vp, vp]),
+    "dmlp_host_pool_end": (i32, []),
+    "dmlp_host_prelude_begin": (i32, [vp, i64, vp, i32, vp, i32, vp, vp, i64, i32, vp]),
+    "dmlp_host_prelude_end": (i32, [i32p, i32p, i32p, i32p]),
+    "dmlp_host_prelude": (i32, [vp, i64, vp, i32p, i32p, vp, i32p, i32p, vp, vp, i64, i32, vp]),
     "dmlp_atomic_fetch_add_i64": (i64, [vp, i64]),
     "dmlp_atomic_store_i64": (None, [vp, i64]),
     "dmlp_cpu_format_debug": (i64, [vp, vp, i32, vp, vp, i64, vp, i64]),

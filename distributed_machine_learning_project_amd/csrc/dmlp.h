@@ -63,8 +63,24 @@ int dmlp_prep_queries(const double* Qx, int64_t Q, int A, const double* mu, int 
 // mu over the first min(N, 4096) rows like dmlp_center; qhi [Q][KT*32] fp16 bits, qn [Q] fp32.
 // dmlp_cpu_prep_queries returns 1 if some |q - mu| is outside the screen's range.
 int dmlp_host_threads(void);
-// fn(ctx, part, parts) on the render pool's workers and the caller (host_prep.cpp)
-void dmlp_host_pool_run(void (*fn)(void*, int, int), void* ctx);
+// fn(ctx, part, parts) on the render pool's workers and the caller (host_prep.cpp); begin / end:
+// on the workers alone while the caller does something else (a pool without workers runs it in
+// end).  -1: rejected, nothing run (a run or a begin inside an open pair, an end without a begin)
+int dmlp_host_pool_run(void (*fn)(void*, int, int), void* ctx);
+int dmlp_host_pool_begin(void (*fn)(void*, int, int), void* ctx);
+int dmlp_host_pool_end(void);
+// The native step's prelude as one job of the pool's workers: k [Q] -> k_stage (null: no copy),
+// the bounds of k (scan_k) and the range of labels [N] (scan_labels), mu (null: none) = the
+// centre of the first min(N, 4096) rows of X (or of the row table Xr), summed in blocks of 256
+// rows so that it does not depend on the pool's size.  begin returns at once, end waits and
+// writes the results; dmlp_host_prelude is both (null bounds pointers: that array is not scanned).
+int dmlp_host_prelude_begin(const int* k, int64_t Q, int* k_stage, int scan_k, const int* labels,
+                            int scan_labels, const double* X, const double* const* Xr, int64_t N,
+                            int A, double* mu);
+int dmlp_host_prelude_end(int* kmin, int* kmax, int* lmin, int* lmax);
+int dmlp_host_prelude(const int* k, int64_t Q, int* k_stage, int* kmin, int* kmax,
+                      const int* labels, int* lmin, int* lmax, const double* X,
+                      const double* const* Xr, int64_t N, int A, double* mu);
 void dmlp_cpu_center(const double* X, int64_t N, int A, double* mu);
 int dmlp_cpu_prep_queries(const double* Qx, int64_t Q, int A, const double* mu, int KT,
                           uint16_t* qhi, float* qn);

@@ -76,24 +76,52 @@ class Pool {
     for (auto& t : th_) t.join();
   }
   int size() const { return n_ + 1; }
-  // f(part, parts) on every worker and the caller; returns when all parts are done
-  void run(const std::function<void(int, int)>& f) {
+  // f(part, parts) on every worker and the caller; returns when all parts are done.  False
+  // (nothing run) between begin and end: the workers are taken.
+  bool run(const std::function<void(int, int)>& f) {
+    if (open_) return false;
     const int parts = size();
-    job_ = &f;
-    pending_.store(parts - 1, std::memory_order_relaxed);
+    publish(&f, parts);
+    f(parts - 1, parts);
+    wait();
+    return true;
+  }
+  // The same job on the workers alone (parts = their number), while the caller does something
+  // else: begin publishes it and returns, end waits for them.  A pool without workers runs
+  // f(0, 1) inside end.  False: a begin inside an open pair, an end without a begin.
+  bool begin(std::function<void(int, int)> f) {
+    if (open_) return false;
+    open_ = true;
+    held_ = std::move(f);
+    if (n_ > 0) publish(&held_, n_);
+    return true;
+  }
+  bool end() {
+    if (!open_) return false;
+    if (n_ > 0) wait();
+    else held_(0, 1);
+    held_ = nullptr;
+    open_ = false;
+    return true;
+  }
+
+ private:
+  void publish(const std::function<void(int, int)>* f, int parts) {
+    job_ = f;
+    parts_ = parts;
+    pending_.store(n_, std::memory_order_relaxed);
     gen_.fetch_add(1);  // seq_cst: a worker either sees it or is counted in sleepers_
     if (sleepers_.load() > 0) {
       { std::lock_guard<std::mutex> g(m_); }
       cv_.notify_all();
     }
-    f(parts - 1, parts);
+  }
+  void wait() {
     for (int spin = 0; pending_.load(std::memory_order_acquire) != 0; ++spin) {
       if (spin < 4096) _mm_pause();
       else std::this_thread::yield();  // a preempted worker: give it the CPU
     }
   }
-
- private:
   bool oversubscribed() const { return n_ + 1 > cpus_; }
   void loop(int t) {
     uint64_t seen = 0;  // gen_ starts at 0: a job dispatched before this thread ran is not missed
@@ -115,7 +143,7 @@ class Pool {
       }
       seen = g;
       if (stop_) return;
-      (*job_)(t, size());
+      (*job_)(t, parts_);
       pending_.fetch_sub(1, std::memory_order_release);
     }
   }
@@ -127,6 +155,9 @@ class Pool {
   std::atomic<int> sleepers_{0};
   std::atomic<bool> stop_{false};
   const std::function<void(int, int)>* job_ = nullptr;
+  int parts_ = 1;
+  std::function<void(int, int)> held_;  // begin's job, alive until end
+  bool open_ = false;                   // between begin and end (the dispatching thread's)
   std::atomic<int> pending_{0};
   int cpus_ = 1 << 30;
 };
@@ -180,6 +211,18 @@ Pool& pool() {
   return p;
 }
 
+// A pass of this file on the pool.  Inside an open begin / end pair (a programming error: the
+// workers are taken) the pool rejects it; the pass then runs on the caller alone, so its result
+// is still whole, and says so once.
+void pool_run(const std::function<void(int, int)>& job) {
+  if (pool().run(job)) return;
+  static std::atomic<bool> told{false};
+  if (!told.exchange(true))
+    std::fprintf(stderr, "[dmlp] host pool: a pass was dispatched between begin and end; it ran "
+                         "on one thread\n");
+  job(0, 1);
+}
+
 // fp32 -> fp16, round to nearest even, subnormals included (|f| < 65504 by the range check;
 // the same bits as F16C's vcvtps2ph with _MM_FROUND_TO_NEAREST_INT).
 inline uint16_t f16_rn(float f) {
@@ -202,8 +245,9 @@ inline uint16_t f16_rn(float f) {
 
 extern "C" int dmlp_host_threads(void) { return pool().size(); }
 
-// (min, max) of an int32 array on the render pool (the native step's label / k scans: ~15 us
-// single-threaded at the bench shape, on the step's critical path); (0, -1) when empty.
+// (min, max) of an int32 array on the render pool (the drop-in's label / k scans: ~15 us
+// single-threaded at the bench shape; the native step scans inside its prelude, below);
+// (0, -1) when empty.
 extern "C" void dmlp_host_i32_range(const int* a, int64_t n, int* lo, int* hi) {
   if (n <= 0) {
     *lo = 0;
@@ -225,7 +269,7 @@ extern "C" void dmlp_host_i32_range(const int* a, int64_t n, int* lo, int* hi) {
   };
   for (int i = 0; i < parts; ++i) { mn[i] = INT32_MAX; mx[i] = INT32_MIN; }
   if (parts == 1) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
   int l = INT32_MAX, h = INT32_MIN;
   for (int i = 0; i < parts; ++i) { l = std::min(l, mn[i]); h = std::max(h, mx[i]); }
   *lo = l;
@@ -234,11 +278,21 @@ extern "C" void dmlp_host_i32_range(const int* a, int64_t n, int* lo, int* hi) {
 
 // fn(ctx, part, parts) on every worker of the render pool and the caller (parts = the pool's
 // size); returns when all parts are done.  For host passes of other modules (the drop-in's
-// index of the harness's vectors) that should not pay a thread start each.
-extern "C" void dmlp_host_pool_run(void (*fn)(void*, int, int), void* ctx) {
+// index of the harness's vectors) that should not pay a thread start each.  -1 (nothing run)
+// between dmlp_host_pool_begin and dmlp_host_pool_end.
+extern "C" int dmlp_host_pool_run(void (*fn)(void*, int, int), void* ctx) {
   std::function<void(int, int)> job = [&](int part, int parts) { fn(ctx, part, parts); };
-  pool().run(job);
+  return pool().run(job) ? 0 : -1;
 }
+
+// The same on the workers alone while the caller does something else (Pool::begin / end):
+// fn(ctx, part, parts) with parts = the number of workers; a pool without workers runs
+// fn(ctx, 0, 1) inside dmlp_host_pool_end.  ctx must stay alive until the end.  -1: a begin (or a
+// run) inside an open pair, an end without a begin — rejected, nothing run.
+extern "C" int dmlp_host_pool_begin(void (*fn)(void*, int, int), void* ctx) {
+  return pool().begin([fn, ctx](int part, int parts) { fn(ctx, part, parts); }) ? 0 : -1;
+}
+extern "C" int dmlp_host_pool_end(void) { return pool().end() ? 0 : -1; }
 
 namespace {
 
@@ -277,6 +331,150 @@ extern "C" void dmlp_cpu_center(const double* X, int64_t N, int A, double* mu) {
 }
 extern "C" void dmlp_cpu_center_rows(const double* const* rows, int64_t N, int A, double* mu) {
   center(TableRows{rows}, N, A, mu);
+}
+
+// ---- the native step's prelude: what dmlp_step needs before its first query chunk renders —
+// the k bounds, the label range, k in page-locked staging, the centre — as ONE job of the pool's
+// workers, begun before the step's first HIP calls and ended behind them (pipeline.hip).
+// The centre is a function of the rows alone, never of the pool's size (ranks with different
+// pools must render the same image): rows in blocks of 256, each block summed left to right per
+// column into its own partial, the partials added in block order, then divided by n.  The
+// threads pick up whole units (a centre block, 16 Ki ints of k or of the labels) from a counter.
+namespace {
+
+constexpr int64_t kCenterRows = 4096, kCenterBlock = 256, kScanUnit = 1 << 14;
+
+template <class Src>
+void center_block(Src src, int64_t r0, int64_t r1, int A, double* out) {
+  for (int a0 = 0; a0 < A; a0 += 64) {
+    const int w = std::min(64, A - a0);
+    double acc[64];
+    const double* r = src(r0) + a0;
+    for (int a = 0; a < w; ++a) acc[a] = r[a];
+    for (int64_t i = r0 + 1; i < r1; ++i) {
+      r = src(i) + a0;
+      for (int a = 0; a < w; ++a) acc[a] += r[a];
+    }
+    std::memcpy(out + a0, acc, sizeof(double) * w);
+  }
+}
+
+struct Prelude {
+  const int* k = nullptr;
+  int* k_stage = nullptr;
+  const int* labels = nullptr;
+  const double* X = nullptr;
+  const double* const* Xr = nullptr;
+  double* mu = nullptr;
+  int64_t Q = 0, N = 0, n = 0;  // n: the centre's rows
+  int A = 0;
+  bool scan_k = false, scan_labels = false, open = false, pooled = false;
+  int64_t nb = 0, nk = 0, nl = 0;  // units: centre blocks, k chunks, label chunks
+  std::atomic<int64_t> next{0};
+  std::vector<double> part;  // [nb][A] block partials
+  int kmn[kMaxPool], kmx[kMaxPool], lmn[kMaxPool], lmx[kMaxPool];  // per thread
+
+  void work(int t) {
+    int kl = INT32_MAX, kh = INT32_MIN, ll = INT32_MAX, lh = INT32_MIN;
+    for (;;) {
+      int64_t u = next.fetch_add(1, std::memory_order_relaxed);
+      if (u < nb) {  // the largest and coldest units first
+        const int64_t r0 = u * kCenterBlock, r1 = std::min(n, r0 + kCenterBlock);
+        if (Xr) center_block(TableRows{Xr}, r0, r1, A, part.data() + u * A);
+        else center_block(FlatRows{X, A}, r0, r1, A, part.data() + u * A);
+        continue;
+      }
+      u -= nb;
+      if (u < nk) {
+        const int64_t b = u * kScanUnit, e = std::min(Q, b + kScanUnit);
+        if (k_stage) std::memcpy(k_stage + b, k + b, sizeof(int) * (size_t)(e - b));
+        if (scan_k)
+          for (int64_t i = b; i < e; ++i) {
+            kl = std::min(kl, k[i]);
+            kh = std::max(kh, k[i]);
+          }
+        continue;
+      }
+      u -= nk;
+      if (u >= nl) break;
+      const int64_t b = u * kScanUnit, e = std::min(N, b + kScanUnit);
+      for (int64_t i = b; i < e; ++i) {
+        ll = std::min(ll, labels[i]);
+        lh = std::max(lh, labels[i]);
+      }
+    }
+    kmn[t] = kl; kmx[t] = kh; lmn[t] = ll; lmx[t] = lh;
+  }
+};
+Prelude g_pre;
+
+}  // namespace
+
+// k [Q] -> k_stage (null: no copy) and, scan_k, its bounds; scan_labels: the range of labels [N];
+// mu (null: no centre) = the centre of the first min(N, 4096) rows of X [N][A] (or, Xr non-null,
+// of that row table).  begin publishes the job to the pool's workers and returns, end waits for
+// it and writes the results: (*kmin, *kmax) when scan_k and Q > 0, (*lmin, *lmax) when
+// scan_labels ((0, -1) for N <= 0), else untouched — an array whose bounds the caller gave is
+// not read for them.  A small job (under 64 Ki values) runs on the caller inside end.
+// -1: a begin inside an open pair or while the pool is taken, an end without a begin.
+extern "C" int dmlp_host_prelude_begin(const int* k, int64_t Q, int* k_stage, int scan_k,
+                                       const int* labels, int scan_labels, const double* X,
+                                       const double* const* Xr, int64_t N, int A, double* mu) {
+  Prelude& p = g_pre;
+  if (p.open) return -1;
+  Q = std::max<int64_t>(Q, 0);
+  N = std::max<int64_t>(N, 0);
+  p.k = k; p.Q = Q; p.k_stage = k ? k_stage : nullptr; p.scan_k = scan_k && k && Q > 0;
+  p.labels = labels; p.scan_labels = scan_labels && labels;
+  p.X = X; p.Xr = Xr; p.N = N; p.A = A;
+  p.mu = (X || Xr || N == 0) && A >= 1 ? mu : nullptr;
+  p.n = std::min(N, kCenterRows);
+  p.nb = p.mu ? (p.n + kCenterBlock - 1) / kCenterBlock : 0;
+  p.nk = p.k_stage || p.scan_k ? (Q + kScanUnit - 1) / kScanUnit : 0;
+  p.nl = p.scan_labels ? (N + kScanUnit - 1) / kScanUnit : 0;
+  p.part.resize((size_t)(p.nb * A));
+  p.next.store(0, std::memory_order_relaxed);
+  for (int i = 0; i < kMaxPool; ++i) {
+    p.kmn[i] = p.lmn[i] = INT32_MAX;
+    p.kmx[i] = p.lmx[i] = INT32_MIN;
+  }
+  const int64_t values = (p.nk ? Q : 0) + (p.nl ? N : 0) + p.nb * kCenterBlock * A * 2;
+  p.pooled = values >= (int64_t)1 << 16;
+  if (p.pooled && !pool().begin([](int part, int) { g_pre.work(part); })) return -1;
+  p.open = true;
+  return 0;
+}
+
+extern "C" int dmlp_host_prelude_end(int* kmin, int* kmax, int* lmin, int* lmax) {
+  Prelude& p = g_pre;
+  if (!p.open) return -1;
+  p.open = false;
+  if (p.pooled) pool().end();
+  else p.work(0);
+  int kl = INT32_MAX, kh = INT32_MIN, ll = INT32_MAX, lh = INT32_MIN;
+  for (int i = 0; i < kMaxPool; ++i) {
+    kl = std::min(kl, p.kmn[i]); kh = std::max(kh, p.kmx[i]);
+    ll = std::min(ll, p.lmn[i]); lh = std::max(lh, p.lmx[i]);
+  }
+  if (p.scan_k) { *kmin = kl; *kmax = kh; }
+  if (p.scan_labels) { *lmin = p.N > 0 ? ll : 0; *lmax = p.N > 0 ? lh : -1; }
+  if (p.mu) {
+    for (int a = 0; a < p.A; ++a) {
+      if (p.nb == 0) { p.mu[a] = 0.0; continue; }
+      double s = p.part[a];
+      for (int64_t b = 1; b < p.nb; ++b) s += p.part[b * p.A + a];
+      p.mu[a] = s / (double)p.n;
+    }
+  }
+  return 0;
+}
+
+extern "C" int dmlp_host_prelude(const int* k, int64_t Q, int* k_stage, int* kmin, int* kmax,
+                                 const int* labels, int* lmin, int* lmax, const double* X,
+                                 const double* const* Xr, int64_t N, int A, double* mu) {
+  if (dmlp_host_prelude_begin(k, Q, k_stage, kmin && kmax, labels, lmin && lmax, X, Xr, N, A, mu))
+    return -1;
+  return dmlp_host_prelude_end(kmin, kmax, lmin, lmax);
 }
 
 namespace {
@@ -354,7 +552,7 @@ int prep_queries(Src src, int64_t Q, int A, const double* mu, int KT, uint16_t* 
     if (!prep_range_any(src, q0, q1, A, mu, W, qhi, qn)) ok.store(0, std::memory_order_relaxed);
   };
   if (Q * (int64_t)A < (int64_t)1 << 14) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
   return ok.load() ? 0 : 1;
 }
 
@@ -470,7 +668,7 @@ extern "C" int dmlp_cpu_rows_i32_rows(const double* const* rows, int64_t nrows, 
     if (!good) ok.store(0, std::memory_order_relaxed);
   };
   if (nrows * (int64_t)A < (int64_t)1 << 14) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
   return ok.load() ? 0 : 1;
 }
 
@@ -482,7 +680,7 @@ extern "C" void dmlp_cpu_gather_rows(const double* const* rows, int64_t nrows, i
     for (int64_t r = a; r < b; ++r) std::memcpy(dst + r * A, rows[r], sizeof(double) * A);
   };
   if (nrows * (int64_t)A < (int64_t)1 << 14) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
 }
 
 // src[0 .. n) -> dst as int32 m with src[i] == fl(m / 1e6) bit for bit; returns 0 when every value
@@ -496,7 +694,7 @@ extern "C" int dmlp_cpu_rows_i32(const double* src, int64_t n, int32_t* dst) {
     if (!r) ok.store(0, std::memory_order_relaxed);
   };
   if (n < (int64_t)1 << 14) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
   return ok.load() ? 0 : 1;
 }
 
@@ -519,7 +717,7 @@ int prep_data_tiles(Src X, int64_t N, int A, const double* mu, int KT, int64_t t
     if (!prep_data_range(X, N, p0, p1, A, mu, KT, xhi, xinit, &mx[part])) ok.store(0);
   };
   if ((t1 - t0) * 64 * (int64_t)A < (int64_t)1 << 14) job(0, 1);
-  else pool().run(job);
+  else pool_run(job);
   float m = 0.0f;
   for (float v : mx) m = std::max(m, v);
   *nmax = m;

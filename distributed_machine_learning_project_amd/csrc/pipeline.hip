@@ -17,7 +17,9 @@
 //                   overflow escalates alone (3-term screen, then exact).
 //
 //   dmlp_step       rows in host memory (flat arrays, or the drop-in's tables of row pointers
-//                   into the harness's own vectors), the call the reference times: the host
+//                   into the harness's own vectors), the call the reference times: the k bounds,
+//                   the label range, k's staging and the centre are one job of the render pool
+//                   behind the call's first HIP calls (dmlp_host_prelude); the host then
 //                   renders the single-term screen's fp16 operands (host_prep.cpp) and copies them
 //                   on a side stream; the screen starts on them while the fp64 rows (lossless
 //                   int32 when every value is a 6-decimal number) cross PCIe behind it; k in
@@ -271,19 +273,52 @@ struct Step {
     const bool want_report = a->report_mode != 0 && a->labels;
     if (a->report_mode == 1 && a->report_cap < dmlp_format_bound((int)Q)) return -2;
     CK(mark(M_ENTER, w.side));
+    const int KT = dmlp_screen_kt(A);
+    // x1_front (below) as far as it is known before the k bounds are: with a one-thread pool and
+    // no plane it also asks dr_auto, which needs them
+    const bool front_sure = !a->exact && N > 0 && KT <= 8 && dmlp_screen_x1_qw(KT) > 0 &&
+                            g_tune.screen == 0 &&
+                            (g_tune.host_ops >= 2 ||
+                             (g_tune.host_ops == 1 && (pl || dr_on() || dmlp_host_threads() >= 2)));
+    // ---- the prelude, one job of the render pool's workers (host_prep.cpp): the k bounds and the
+    // label range where the caller gave none, k into its page-locked staging, the centre (with a
+    // plane: rank 0's) — while this thread issues the HIP calls that need none of them
+    const bool scan_k = Q > 0 && a->kmax < a->kmin;
+    const bool scan_lab = a->labels && a->label_hi <= a->label_lo;
+    const bool mu_here = front_sure && (!pl || pl->rank == 0) && (Q > 0 || pl);
+    int* kh = front_sure && Q > 0 ? w.kk_h.get(Q) : nullptr;
+    double* mu = front_sure ? w.s_mu.get(A) : nullptr;
+    unsigned* words = w.dwords.get(kW_N);
+    struct Prelude {  // (a throw between begin and end must not leave the pool's workers taken)
+      bool open = false;
+      int end(int* k0, int* k1, int* l0, int* l1) {
+        open = false;
+        return dmlp_host_prelude_end(k0, k1, l0, l1);
+      }
+      ~Prelude() {
+        int x[4];
+        if (open) end(x, x + 1, x + 2, x + 3);
+      }
+    } pre;
+    if (dmlp_host_prelude_begin(a->k, Q, kh, scan_k, a->labels, scan_lab, a->X, a->Xr, N, A,
+                                mu_here ? mu : nullptr) != 0)
+      return -1;
+    pre.open = true;
     // the caller's stream may hold work on the buffers of the previous call: the side stream's
     // copies into them start after it
     CK(hipEventRecord(w.ev_ops, st));
     CK(hipStreamWaitEvent(w.side, w.ev_ops, 0));
-    int kmin = a->kmin, kmax = a->kmax;
-    if (Q > 0 && kmax < kmin) {  // k bounds not given: one pass on the render pool
-      dmlp_host_i32_range(a->k, Q, &kmin, &kmax);
+    // the step's words (norm, bad, ready words, counters, overflow) zeroed by one DMA copy on the
+    // side stream ahead of the operands, so nothing sits on `st` between the operands' event and
+    // the screen
+    if (Q > 0) CK(dma_zero(words, kW_N * sizeof(unsigned), w.side));
+    int kmin = a->kmin, kmax = a->kmax, lmin = 0, lmax = -1;
+    if (pre.end(&kmin, &kmax, &lmin, &lmax) != 0) return -1;
+    if (scan_k) {  // k bounds not given
       a->kmin = kmin;
       a->kmax = kmax;
     }
-    if (a->labels && a->label_hi <= a->label_lo) {  // label range not given: the same
-      int lmin = 0, lmax = -1;
-      if (N > 0) dmlp_host_i32_range(a->labels, N, &lmin, &lmax);
+    if (scan_lab) {  // label range not given
       // lmax == INT_MAX: [lo, lmax + 1) has no int form; (0, 0) makes every vote count instead
       const bool fits = lmax < INT_MAX;
       a->label_lo = N > 0 && fits ? lmin : 0;
@@ -291,7 +326,6 @@ struct Step {
     }
     const int kst = a->kstride > 0 ? a->kstride : std::max(1, Q ? kmax : 1);
     if (Q > 0 && kmax > kst) return -3;
-    const int KT = dmlp_screen_kt(A);
     const int64_t nt = (N + 63) / 64, W = (int64_t)KT * 32;
     // outputs (the caller's device tensors, or workspace)
     double* od = a->out_d ? a->out_d : w.d_od.get((size_t)std::max<int64_t>(Q, 1) * kst);
@@ -316,17 +350,14 @@ struct Step {
       w.text_len = 0;
       // no queries here, but this rank's share of the node render plane is still owed
       if (pl && pl->rank < pl->renderers && N > 0) {
-        double* mu = w.s_mu.get(A);
-        if (x1_front) {
+        if (x1_front) {  // (== front_sure with a plane: rank 0's centre is the prelude's)
           if (pl->rank == 0) {
-            if (a->Xr) dmlp_cpu_center_rows(a->Xr, std::min<int64_t>(N, 4096), A, mu);
-            else dmlp_cpu_center(a->X, std::min<int64_t>(N, 4096), A, mu);
             CKL(dmlp_plane_put_mu(pl, A, mu));
           } else if (dmlp_plane_get_mu(pl, A, mu) != 0) {
             throw Fail{-9};
           }
         }
-        render_plane_share(mu, x1_front ? 1 : 2, a->X32d ? 1 : 2);
+        render_plane_share(x1_front ? mu : w.s_mu.get(A), x1_front ? 1 : 2, a->X32d ? 1 : 2);
       }
       return 0;
     }
@@ -339,19 +370,18 @@ struct Step {
     if (early && !dr_early_ok(KT, kmax)) dr = false;
     const int NS = early ? (int)std::min<int64_t>(kEarlySlices, nt) : 0;
     const int rt = early ? (int)((nt + NS - 1) / NS) : 1;  // image tiles per early slice
-    unsigned* words = w.dwords.get(kW_N);
     unsigned* rdy = words + kW_RDY;
     unsigned* estats = words + kW_EST;
     HostOps hx;
     bool use_hx = false, early_bad = false;
-    // ---- the step's words (norm, bad, ready words, counters, overflow) zeroed by one DMA copy, and
-    // on the all-class-a path k on the device — both on the side stream ahead of the operands,
-    // so nothing sits on `st` between the operands' event and the screen
-    CK(dma_zero(words, kW_N * sizeof(unsigned), w.side));
+    // ---- on the all-class-a path k on the device, on the side stream ahead of the operands like
+    // the words' zero copy (the prelude staged it, unless the front was not sure by then)
     int* kd_pre = nullptr;
     if (x1_front && all_a) {
-      int* kh = w.kk_h.get(Q);
-      pool_memcpy(kh, a->k, Q * sizeof(int));
+      if (!kh) {
+        kh = w.kk_h.get(Q);
+        pool_memcpy(kh, a->k, Q * sizeof(int));
+      }
       kd_pre = w.kdev.get(Q);
       CK(dmlp::dma_copy(kd_pre, kh, Q * sizeof(int), w.side));
     }
@@ -492,16 +522,17 @@ struct Step {
       unsigned* xnm_h = w.sx_nm.get(2 + kEarlySlices);
       uint16_t* qhi_h = w.sq_hi.get(Q * W);
       float* qn_h = w.sq_n.get(Q);
-      double* mu = w.s_mu.get(A);
       short* xhi = w.dx_hi.get(nt * 64 * W);
       float* xin = w.dx_in.get(nt * 64);
       short* qhi = w.dq_hi.get(Q * W);
       float* qn = w.dq_n.get(Q);
+      if (!mu) mu = w.s_mu.get(A);
       if (pl && pl->rank != 0) {
         if (dmlp_plane_get_mu(pl, A, mu) != 0) throw Fail{-9};  // rank 0's centre, same bits
       } else {
-        if (a->Xr) dmlp_cpu_center_rows(a->Xr, std::min<int64_t>(N, 4096), A, mu);
-        else dmlp_cpu_center(a->X, std::min<int64_t>(N, 4096), A, mu);
+        if (!mu_here)  // (the front was not sure before the prelude: the same centre now)
+          CKL(dmlp_host_prelude(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                a->X, a->Xr, N, A, mu));
         if (pl) CKL(dmlp_plane_put_mu(pl, A, mu));
       }
       auto h2d_tiles = [&](int64_t t0, int64_t t1, const double* qx, const double* const* qr,
