@@ -427,23 +427,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
   // ---- D-deep register ring of step fragments + double-buffered accumulators
   bf16x8 A[D][KT];
   f32x4 Xi[D];
+  // Both start at -inf: the loop's first epilogue (of "step -1", on acc[1] and pm) then needs no
+  // j > 0 branch, which would split a step's MFMAs and its epilogue VALU into two basic blocks
+  // that no scheduler interleaves.  -inf >= h is false for every threshold (h >= -FLT_MAX), so
+  // that epilogue never appends.
   f32x4 acc[2][CT];
   float pm[CT];  // PAIR: the pair's first step's 4-row maxima
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    acc[1][ct] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    pm[ct] = -INFINITY;
+  }
 #define DMLP_LOADA(J, R)                                                                        \
   do {                                                                                          \
     _Pragma("unroll") for (int kt = 0; kt < KT; ++kt)                                           \
       A[R][kt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(              \
           xr, lane * 16 + kt * ks, (J) * (KT * ks), 0));                                        \
   } while (0)
-#define DMLP_LOADX(J, R)                                                                        \
+  // step R of the window whose ring slot xrd points into: one base register, immediate offsets
+#define DMLP_LOADX(R)                                                                           \
   do {                                                                                          \
-    Xi[R] = *(__attribute__((address_space(3))) const f32x4*)(size_t)(                          \
-        xrb + (((J) >> 2) & 1) * 256 + ((J) & 3) * 64 + kg * 16);                               \
+    Xi[R] = *(__attribute__((address_space(3))) const f32x4*)(size_t)(xrd + (R) * 64);          \
   } while (0)
 #define DMLP_LOAD(J, R)                                                                         \
   do {                                                                                          \
     DMLP_LOADA(J, R);                                                                           \
-    DMLP_LOADX(J, R);                                                                           \
+    DMLP_LOADX(R);                                                                              \
   } while (0)
 #define DMLP_MFMA(R, AB)                                                                        \
   do {                                                                                          \
@@ -451,6 +460,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
       acc[AB][ct] = mfma16<F16>(A[R][0], bh[ct][0], Xi[R]);                                     \
       _Pragma("unroll") for (int kt = 1; kt < KT; ++kt)                                         \
         acc[AB][ct] = mfma16<F16>(A[R][kt], bh[ct][kt], acc[AB][ct]);                           \
+    }                                                                                           \
+  } while (0)
+  // PAIR: the explicit interleave.  A ring slot's basic block holds its CT * KT MFMAs and the
+  // unconditional epilogue VALU of the step before it; left alone, the scheduler issues the MFMAs
+  // back to back and the VALU behind them, where the wave can use none of its own MFMA issue
+  // stalls (a 16x16x32 MFMA holds the vector issue for 8 of its 16 cycles).  The group barriers
+  // put NV of them behind each column tile's MFMAs.  The work of a pair is split evenly: the first
+  // step's four 4-row maxima (pinned to that slot by the empty asm) and the fill compares go
+  // under the second step's MFMAs, the second step's v_max3 and the hit compares under the next
+  // pair's first step.  NV = 6 packs a slot's 13-14 VALU behind its first two MFMAs, so every
+  // compare has issued before the last two: their SGPR results, the s_or chain and the branch
+  // resolve under those MFMAs instead of behind them (an even spread, NV = 3, measured no
+  // better than no interleave at all: profiles/r14a_screen_interleave.txt).  The order of every
+  // compare relative to grow() and to the compactions is the one of the plain sequence (grow()
+  // runs at the loop head, before the slot whose compares follow it), so a compare never sees a
+  // threshold higher than before and the screen's bound argument is untouched.
+  constexpr int NV = 6;  // VALU per MFMA gap (2 - 7 measured)
+#define DMLP_INTERLEAVE()                                                                       \
+  do {                                                                                          \
+    if constexpr (PAIR) {                                                                       \
+      _Pragma("unroll") for (int ct = 0; ct < CT; ++ct) {                                       \
+        __builtin_amdgcn_sched_group_barrier(0x8 /* MFMA */, KT, 0);                            \
+        __builtin_amdgcn_sched_group_barrier(0x2 /* VALU */, NV, 0);                            \
+      }                                                                                         \
     }                                                                                           \
   } while (0)
 #define DMLP_EPILOGUE(AB, J, ODD)                                                               \
@@ -469,9 +502,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
       else                                                                                      \
         m_[ct] = fmaxf(fmaxf(fmaxf(acc[AB][ct][0], acc[AB][ct][1]), acc[AB][ct][2]),            \
                        acc[AB][ct][3]);                                                         \
-      if (first_) pm[ct] = m_[ct];                                                              \
-      else any_ |= __builtin_amdgcn_ballot_w64(m_[ct] >= h[ct]);                                \
+      if (first_) {                                                                             \
+        pm[ct] = m_[ct];                                                                        \
+        asm volatile("" : "+v"(pm[ct])); /* computed in this slot, not sunk into the next */    \
+      } else {                                                                                  \
+        any_ |= __builtin_amdgcn_ballot_w64(m_[ct] >= h[ct]);                                   \
+      }                                                                                         \
     }                                                                                           \
+    if (!first_) DMLP_INTERLEAVE();                                                             \
     if (!first_ && (C::D == 4 || (J) < nsteps) && any_) {                                       \
       unsigned gl_ = PAIR ? (unsigned)(((J) >> 1) * 4 + kg) : (unsigned)((J) * 4 + kg);        \
       asm volatile("" : "+v"(gl_)); /* one VGPR: each key is a single v_and_or / v_bfi */       \
@@ -493,6 +531,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
     unsigned long long trig = 0;                                                                \
     _Pragma("unroll") for (int ct = 0; ct < CT; ++ct)                                           \
       trig |= __builtin_amdgcn_ballot_w64(addr[ct] > lim[ct]);                                  \
+    DMLP_INTERLEAVE(); /* (PAIR: the checks sit in the slots of the pairs' second steps) */     \
     if (trig) compact(false);                                                                   \
   } while (0)
 
@@ -529,12 +568,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
   // texture path — which the fragment loads keep busy (profiles/r2b_screen_x1_ta_pmc.txt).
   static_assert(D == 4, "the C-operand ring assumes a 4-deep fragment ring");
   const unsigned xrb = C::LDS - C::XRING;  // LDS byte offset of the ring
+  // this lane's read and write addresses in the ring slot in use: both flip slots once per
+  // window (one v_xor each per 4 steps) and every access adds an immediate offset, instead of
+  // one address instruction per step formed from the step number
+  static_assert((xrb & 511u) == 0, "the slot flip is an XOR with 256");
+  unsigned xrd = xrb + kg * 16, xwr = xrb + lane * 4;
   float xw = 0.0f;                          // the next window's float of this lane
   auto xwin = [&](int w) __attribute__((always_inline)) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ir, lane * 4, w * 256, 0));
   };
   if (nsteps > 0) {
-    *(__attribute__((address_space(3))) float*)(size_t)(xrb + lane * 4) = xwin(0);
+    *(__attribute__((address_space(3))) float*)(size_t)xwr = xwin(0);
     xw = xwin(1);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the ring reads stay after it
     // prologue in the loop's issue order (A, Xi per step), so the waitcnt at the loop head is
@@ -577,13 +621,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
         if (r == 0) {
           // window j0/4 + 1 (steps j0 + 4 .. j0 + 7) into the slot window j0/4 - 1 used (every
           // read of it is done: those steps were loaded into the register ring already)
-          *(__attribute__((address_space(3))) float*)(size_t)(
-              xrb + (((j0 >> 2) + 1) & 1) * 256 + lane * 4) = xw;
+          xrd ^= 256u;
+          xwr ^= 256u;
+          // (opaque: derived from j0 again, each read would get its own address instruction)
+          asm volatile("" : "+v"(xrd), "+v"(xwr));
+          *(__attribute__((address_space(3))) float*)(size_t)xwr = xw;
           xw = xwin((j0 >> 2) + 2);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         }
         DMLP_LOAD(j + D, r);
-        if (j > 0) DMLP_EPILOGUE((r + 1) & 1, j - 1, (r + 1) & 1);
+        DMLP_EPILOGUE((r + 1) & 1, j - 1, (r + 1) & 1);  // (j = 0: of -inf, see acc)
         // (PAIR: the appends come at even r — the pairs end at odd steps — and CHECK = 2 puts a
         // check one step behind each)
         if (r % CHECK == CHECK - 1) DMLP_CHECK();
@@ -598,6 +645,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
 #undef DMLP_LOADX
 #undef DMLP_MFMA
 #undef DMLP_EPILOGUE
+#undef DMLP_INTERLEAVE
 #undef DMLP_CHECK
   // final threshold over everything buffered, then the candidate ids
   compact(true);
