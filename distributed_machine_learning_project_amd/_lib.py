@@ -121,6 +121,9 @@ _SIGS = {
     "dmlp_format_bound": (i64, [i32]),
     "dmlp_format_scratch": (i64, [i32]),
     "dmlp_format_report": (i32, [vp, i32, i32, vp, vp, vp]),
+    "dmlp_format_report_at": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "dmlp_fill_f64": (i32, [vp, i64, C.c_double, vp]),
+    "dmlp_offset_ids": (i32, [vp, i64, i32, vp]),
     "dmlp_cpu_knn": (i32, [vp, i64, i32, vp, i64, vp, i32, vp, vp, i32]),
     "dmlp_cpu_finalize": (i32, [vp, vp, i32, vp, i64, vp, vp, vp]),
     "dmlp_cpu_merge": (i32, [vp, vp, i32, i64, i32, vp, i64, vp, vp, i32]),

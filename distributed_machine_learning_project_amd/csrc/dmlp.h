@@ -52,10 +52,17 @@ int dmlp_refine_groups_exact(int cap, const int* cand_ids, const int* cand_cnt, 
 // X [N][A] fp64 -> fragment-native bf16 hi/lo tiles (64 points x 32*KT attrs per tile),
 // xinit[n_tiles*64] = -(|x-mu|^2)/2 (fp32; -inf for padding), xnmax_bits = max |x-mu|^2 (fp32
 // bits), bad |= 1 if any value is non-finite or too large for the bf16x3 screen.
+// xfrag: every 16-bit word of the n_tiles * 64 * KT * 64 of the image is written (padding rows
+// and attributes >= A as 0; a flagged element as 0, left out of the norms), xinit: n_tiles * 64
+// floats, nothing else.  *xnmax_bits and *bad ACCUMULATE (atomicMax / atomicOr into the word's
+// value): the caller zeroes them.  KT < 1 or A > 32 KT returns -1 before any launch.
 int dmlp_prep_data(const double* X, int64_t N, int A, const double* mu, int KT, void* xfrag,
                    float* xinit, unsigned* xnmax_bits, unsigned* bad, void* stream);
 
-// Qx [Q][A] fp64 -> qhi/qlo [Q][32*KT] bf16, qn[Q] = |q-mu|^2 (fp32).
+// Qx [Q][A] fp64 -> qhi/qlo [Q][32*KT] bf16, qn[Q] = |q-mu|^2 (fp32).  hi = bf16(fp32(c)), lo =
+// bf16(fp32(c - hi)) with c - hi taken in fp64 (round to nearest even; what
+// dmlp_screen_x1_bound2(hl = 2) relies on).  Every word of the Q rows is written (attributes >= A
+// as 0), nothing else; *bad accumulates as in dmlp_prep_data; -1 on the same arguments.
 int dmlp_prep_queries(const double* Qx, int64_t Q, int A, const double* mu, int KT, void* qhi,
                       void* qlo, float* qn, unsigned* bad, void* stream);
 
@@ -106,7 +113,9 @@ int dmlp_host_ops_h2d_tiles_rows(const double* const* Xr, int64_t N, int64_t t0,
 int dmlp_cpu_rows_i32_rows(const double* const* rows, int64_t nrows, int A, int32_t* dst);
 void dmlp_cpu_gather_rows(const double* const* rows, int64_t nrows, int A, double* dst);
 // Lossless 6-decimal transfer: int32 m with x == fl(m / 1e6) bit for bit (0 = every value
-// passed, 1 = ship fp64), and the device reconstruction of the fp64 rows.
+// passed, 1 = ship fp64), and the device reconstruction of the fp64 rows: dst[i] = the correctly
+// rounded m / 1e6 for i < n and nothing past dst[n); src and dst 16-byte aligned (-1 before any
+// launch otherwise).
 int dmlp_cpu_rows_i32(const double* src, int64_t n, int32_t* dst);
 int dmlp_rows_from_i32(const int* src, int64_t n, double* dst, void* stream);
 // The single-term screen's fp16 operands rendered on the device from rows that landed (prep.hip
@@ -116,6 +125,8 @@ int dmlp_rows_from_i32(const int* src, int64_t n, double* dst, void* stream);
 // copy xrow (nullable), rounded-up max norm -> atomicMax(*nmax); mode 1: queries -> qhi img
 // [row][KT 32], qn xq.  |x - mu| out of the fp16 range sets *bad (nullable).  done / rdy
 // (nullable, *done zeroed by the caller): the last workgroup publishes *rdy = 1.
+// *nmax and *bad accumulate over calls (atomicMax / atomicOr): the caller zeroes them.  n <= 0
+// returns 0 and writes nothing; mode 0 with r0 or n not a multiple of 64 returns -1.
 int dmlp_render_rows(int KT, int A, const int* src32, const double* src64, int64_t r0, int64_t n,
                      int64_t nvalid, const double* mu, double* dst64, int mode, void* img,
                      float* xq, void* xrow, unsigned* nmax, unsigned* bad, unsigned* done,
@@ -467,19 +478,25 @@ int dmlp_finalize(const double* d, const int* ids, int kstride, const int* qk, c
                   int nq, const int* labels, int label_lo, int label_hi, int* out_label,
                   uint64_t* out_cs, void* stream);
 
+// p[i] = v, i < n.  ids[i] += off where ids[i] >= 0 (0 included; the padding -1 is kept), i < n;
+// off = 0 launches nothing.  Nothing outside [0, n) is written.
 int dmlp_fill_f64(double* p, int64_t n, double v, void* stream);
 int dmlp_offset_ids(int* ids, int64_t n, int off, void* stream);
 
 // ---------------------------------------------------------------- device: report formatting (K7)
 // "Query <qid> checksum: <cs>\n" for q < nq into out (needs dmlp_format_bound bytes).
 // line_off[dmlp_format_scratch(nq)] is int64 scratch: line_off[0..nq] receives the line offsets
-// (line_off[nq] = total bytes), the tail holds the per-block sums of the scan.
+// (line_off[nq] = total bytes), the tail holds the per-block sums of the scan.  Only the bytes of
+// the text, [line_off[0], line_off[nq]), are written.  out must be 4-byte aligned (the dword
+// stores are aligned on the byte offset in out): -1 before any launch otherwise.  nq <= 0 returns
+// 0 and writes nothing, line_off included.
 int64_t dmlp_format_bound(int nq);
 int64_t dmlp_format_scratch(int nq);
 int dmlp_format_report(const uint64_t* cs, int nq, int qid_base, int64_t* line_off, char* out,
                        void* stream);
 // ... with the lines starting at byte *base of out (base: device int64, null = 0); line_off then
-// holds absolute offsets (line_off[nq] = the end of this run's text)
+// holds absolute offsets (line_off[nq] = the end of this run's text); a part writes no byte of
+// its neighbours, whatever the alignment of its ends, so parts may be issued in any order
 int dmlp_format_report_at(const uint64_t* cs, int nq, int qid_base, int64_t* line_off, char* out,
                           const int64_t* base, void* stream);
 

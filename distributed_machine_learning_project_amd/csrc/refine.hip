@@ -1782,10 +1782,13 @@ extern "C" int dmlp_format_report(const uint64_t* cs, int nq, int qid_base, int6
 }
 
 // The same, the lines starting at byte *base of out (device word; null: 0): a report rendered in
-// query parts, each part's base = the previous part's line_off[nq] (its absolute end)
+// query parts, each part's base = the previous part's line_off[nq] (its absolute end).
+// k_fmt_write aligns its dword stores on the byte offset in out, not on the address: out must be
+// 4-byte aligned (-1 before any launch otherwise, like dmlp_rows_from_i32's operands).
 extern "C" int dmlp_format_report_at(const uint64_t* cs, int nq, int qid_base, int64_t* line_off,
                                      char* out, const int64_t* base, void* stream) {
   if (nq <= 0) return 0;
+  if ((uintptr_t)out & 3) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int nb = (nq + kFmtBlock - 1) / kFmtBlock;
   int64_t* blocksum = line_off + nq + 1;
