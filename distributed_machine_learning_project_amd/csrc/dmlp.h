@@ -478,6 +478,27 @@ int dmlp_finalize(const double* d, const int* ids, int kstride, const int* qk, c
                   int nq, const int* labels, int label_lo, int label_hi, int* out_label,
                   uint64_t* out_cs, void* stream);
 
+// ---- device: vote curve (prefix votes of a sorted neighbour list)
+// Row q < nq: slots e in [0, min(qk[q], kstride, 256)) of ids[q * kstride ...] are read (and of d
+// when out_d is given; d may be null otherwise).  An entry is kept when ids[e] >= 0 and ids[e] !=
+// skip[q] (skip nullable; a negative skip[q] excludes nothing; negative ids are skipped wherever
+// they sit); kept entries keep their order, m = min(#kept, kcap).
+//   out_label[q * kcap + j], j < m: the vote over the first j + 1 kept entries (max count, ties ->
+//     larger label: what dmlp_finalize returns for that prefix); j in [m, kcap) repeats slot m - 1,
+//     or holds -1 when m == 0.  Labels are any int: no range is taken, no histogram used.
+//   out_d / out_i (both null or both given) [nq][kcap]: the kept entries j < m, then (+inf, -1):
+//     the list without the skipped id.
+//   truth / hits (both null or both given; hits[kcap] on the device): hits[j] += the number of
+//     rows with out_label[q * kcap + j] == truth[q], for every j < kcap.  ACCUMULATES like
+//     ovf_count (one atomicAdd per j per workgroup): the caller zeroes it.
+// Every slot of the nq * kcap outputs is written, nothing outside them.  nq <= 0 returns 0 and
+// writes nothing; kcap outside [1, dmlp_vote_curve_kmax()], kstride < 1 or a half-given pair
+// returns -1 before any launch.
+int dmlp_vote_curve_kmax(void);   // 256
+int dmlp_vote_curve(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                    const int* skip, const int* labels, int kcap, int* out_label, double* out_d,
+                    int* out_i, const int* truth, unsigned long long* hits, void* stream);
+
 // p[i] = v, i < n.  ids[i] += off where ids[i] >= 0 (0 included; the padding -1 is kept), i < n;
 // off = 0 launches nothing.  Nothing outside [0, n) is written.
 int dmlp_fill_f64(double* p, int64_t n, double v, void* stream);
@@ -507,6 +528,10 @@ int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* q
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,
                    const int* qk, int64_t Q, double* out_d, int* out_i, int kout);
+// dmlp_vote_curve's contract on the host (the 256-slot clamp included); hits accumulates.
+int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
+                        const int* skip, const int* labels, int kcap, int* out_label,
+                        double* out_d, int* out_i, const int* truth, unsigned long long* hits);
 int dmlp_kdtree_knn(const double* X, int64_t N, int A, const double* Qx, int64_t Q,
                     const int* qk, int kstride, double* out_d, int* out_i);
 // Text report, host side.  Returns bytes written (buffer must hold 48*Q bytes).

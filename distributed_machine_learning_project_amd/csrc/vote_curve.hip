@@ -1,0 +1,166 @@
+// vote_curve.hip — the vote of every prefix of a sorted neighbour list (dmlp.h: vote curve).
+//
+// The lists come out of the search sorted by (dist asc, id desc), so the vote for every k <= kmax
+// is a function of ONE list.  For kept entry e let c_e = #{kept e' <= e with e's label} and
+// key_e = (c_e << 32) | (label_e ^ 0x80000000), wave_vote_by's key: the largest key over a prefix
+// names its vote (max count, ties -> larger label), because the running count of the winning
+// label is reached by exactly one entry of the prefix.  The curve is an inclusive prefix max of
+// the keys — no label histogram, so any int is a label.
+//
+// One wave per query row, lane L holding slots 4L .. 4L + 3: ballot / popcount compaction of the
+// kept entries (the row's own id and padding dropped), labels staged in a 1 KiB LDS strip per
+// wave, counts by broadcast reads of that strip, the prefix max as an in-lane scan plus a 6-step
+// cross-lane scan.  Rows are taken grid-stride, so the per-k hit counts stay in registers over a
+// wave's rows, meet in LDS once per workgroup and reach memory as one atomicAdd per k.
+#include "dmlp.h"
+#include "dmlp_device.h"
+
+#include <math.h>
+
+#include <algorithm>
+
+namespace {
+
+constexpr int kCurveMax = 256;  // slots per row = 64 lanes x 4 = the workgroup's threads
+constexpr int kCurveWaves = 4;
+constexpr int kCurveBlocks = 2048;
+
+__device__ __forceinline__ long long max64(long long a, long long b) { return a > b ? a : b; }
+
+__global__ __launch_bounds__(256) void k_vote_curve(
+    const double* __restrict__ d, const int* __restrict__ ids, int kstride,
+    const int* __restrict__ qk, int nq, const int* __restrict__ skip,
+    const int* __restrict__ labels, int kcap, int* __restrict__ out_label,
+    double* __restrict__ out_d, int* __restrict__ out_i, const int* __restrict__ truth,
+    unsigned long long* __restrict__ hits) {
+  __shared__ __attribute__((aligned(16))) int s_lab[kCurveWaves][kCurveMax];
+  __shared__ int s_hits[kCurveMax];
+  const int lane = dmlp::lane_id(), wave = threadIdx.x >> 6;
+  if (hits) {
+    s_hits[threadIdx.x] = 0;
+    __syncthreads();
+  }
+  int* strip = s_lab[wave];
+  const unsigned long long lt = dmlp::lanemask_lt();
+  int hacc[4] = {0, 0, 0, 0};
+  for (int64_t q = (int64_t)blockIdx.x * kCurveWaves + wave; q < nq;
+       q += (int64_t)gridDim.x * kCurveWaves) {
+    const int n = min(min(qk[q], kstride), kCurveMax);  // (a negative k reads nothing)
+    const int sk = skip ? skip[q] : -1;                 // (kept ids are >= 0: -1 excludes nothing)
+    const int64_t in0 = q * kstride, out0 = q * kcap;
+    int id[4], lb[4];
+    bool kept[4];
+    unsigned long long b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * lane + i;
+      id[i] = e < n ? ids[in0 + e] : -1;
+      kept[i] = id[i] >= 0 && id[i] != sk;
+      lb[i] = kept[i] ? labels[id[i]] : 0;
+      b[i] = __ballot(kept[i]);
+    }
+    int pos = 0, M = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      pos += __popcll(b[i] & lt);
+      M += __popcll(b[i]);
+    }
+    const int m = min(M, kcap);
+    dmlp::wave_sync();  // the last row's strip reads come first
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (kept[i]) {
+        strip[pos] = lb[i];  // (pos <= 255)
+        if (out_i && pos < kcap) {
+          out_i[out0 + pos] = id[i];
+          out_d[out0 + pos] = d[in0 + 4 * lane + i];
+        }
+        ++pos;
+      }
+    }
+    if (out_i) {
+      for (int j = m + lane; j < kcap; j += 64) {
+        out_i[out0 + j] = -1;
+        out_d[out0 + j] = INFINITY;
+      }
+    }
+    dmlp::wave_sync();
+    // the compacted list: lane L now holds kept entries 4L .. 4L + 3
+    int cl[4], c[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      cl[i] = 4 * lane + i < M ? strip[4 * lane + i] : 0;
+      c[i] = 0;
+    }
+    const int4* s4 = reinterpret_cast<const int4*>(strip);
+    for (int t = 0; 4 * t < M; ++t) {
+      const int4 v = s4[t];  // one address for the wave: a broadcast read
+      const int r = 4 * lane - 4 * t;  // entry j' = 4t + u counts for j = 4L + i when u <= r + i
+      // (slots of the strip past M hold stale labels: they pair only with j >= M, whose key is
+      // dropped below)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        c[i] += (int)((v.x == cl[i]) & (0 <= r + i)) + (int)((v.y == cl[i]) & (1 <= r + i)) +
+                (int)((v.z == cl[i]) & (2 <= r + i)) + (int)((v.w == cl[i]) & (3 <= r + i));
+      }
+    }
+    long long key[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      key[i] = 4 * lane + i < M
+                   ? ((long long)c[i] << 32) | (long long)((unsigned)cl[i] ^ 0x80000000u)
+                   : -1ll;
+      if (i) key[i] = max64(key[i], key[i - 1]);
+    }
+    long long incl = key[3];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long t = __shfl_up(incl, o);
+      if (lane >= o) incl = max64(incl, t);
+    }
+    long long excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = -1ll;
+    const int tr = truth ? truth[q] : 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = 4 * lane + i;
+      if (j < kcap) {
+        // slots past the kept entries carry the last prefix's key on: the label repeats, and a
+        // row without a kept entry holds -1 throughout
+        const long long kj = max64(key[i], excl);
+        const int lab = kj < 0 ? -1 : (int)((unsigned)(kj & 0xffffffffll) ^ 0x80000000u);
+        out_label[out0 + j] = lab;
+        hacc[i] += (int)(truth != nullptr && lab == tr);
+      }
+    }
+  }
+  if (hits) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (hacc[i]) atomicAdd(&s_hits[4 * lane + i], hacc[i]);
+    __syncthreads();
+    const int cnt = s_hits[threadIdx.x];
+    if ((int)threadIdx.x < kcap && cnt) atomicAdd(&hits[threadIdx.x], (unsigned long long)cnt);
+  }
+}
+
+}  // namespace
+
+extern "C" int dmlp_vote_curve_kmax(void) { return kCurveMax; }
+
+extern "C" int dmlp_vote_curve(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                               const int* skip, const int* labels, int kcap, int* out_label,
+                               double* out_d, int* out_i, const int* truth,
+                               unsigned long long* hits, void* stream) {
+  if (nq <= 0) return 0;
+  if (kcap < 1 || kcap > kCurveMax || kstride < 1) return -1;
+  if ((out_d == nullptr) != (out_i == nullptr) || (truth == nullptr) != (hits == nullptr))
+    return -1;
+  if (!ids || !qk || !labels || !out_label || (out_d && !d)) return -1;
+  const int blocks = std::min((nq - 1) / kCurveWaves + 1, kCurveBlocks);
+  hipLaunchKernelGGL(k_vote_curve, dim3(blocks), dim3(64 * kCurveWaves), 0, (hipStream_t)stream,
+                     d, ids, kstride, qk, nq, skip, labels, kcap, out_label, out_d, out_i, truth,
+                     hits);
+  DMLP_LAUNCH_CHECK();
+  return 0;
+}

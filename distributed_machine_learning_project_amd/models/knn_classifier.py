@@ -4,6 +4,10 @@
     dist, ids = clf.kneighbors(Q, k)         # k: int or per-query array
     labels = clf.predict(Q, k)               # majority vote, ties -> larger label
     cs = clf.checksums(Q, k)                 # reference FNV-1a report checksums
+    curve = clf.predict_curve(Q, kmax)       # [Q, kmax]: column k - 1 == predict(Q, k)
+    dist, ids = clf.loo_kneighbors(kmax)     # neighbours of the dataset's own rows, self excluded
+    hits, N = clf.loo_curve(kmax)            # leave-one-out hits of every k <= kmax
+    best_k, acc = clf.select_k(kmax)         # the smallest k with the best leave-one-out accuracy
 
 Semantics are the reference's: exact fp64 squared-L2 distances summed left to
 right without FMA, neighbours ordered by (distance asc, id desc).  On a GPU the dataset is
@@ -94,6 +98,95 @@ class KNNClassifier:
 
     def checksums(self, Q, k):
         return self._run(Q, k, finalize=True)[3]
+
+    # ------------------------------------------------------------ choosing k
+    # The lists are sorted, so the vote for every k <= kmax is a function of one list: one search
+    # at kmax, then the vote-curve kernel (csrc/vote_curve.hip; dmlp_cpu_vote_curve on a CPU).
+    def predict_curve(self, Q, kmax: int):
+        """int32 [Q, kmax]: column k - 1 is predict(Q, k), bit for bit, from ONE search at kmax."""
+        kmax = int(kmax)
+        if not 1 <= kmax <= K.VOTE_CURVE_KMAX:
+            raise ValueError(f"kmax must be in [1, {K.VOTE_CURVE_KMAX}]")
+        Q = np.ascontiguousarray(Q, np.float64)
+        kk = np.full(Q.shape[0], kmax, np.int32)
+        if self.on_gpu:
+            torch = _torch()
+            r = K.knn_gpu(self._ds, torch.from_numpy(Q).cuda(), kk, finalize=False,
+                          exact=self.exact)
+            return K.vote_curve_gpu(r.ids, kk, self._ds.labels, kmax)[0].cpu().numpy()
+        _, i = K.knn_cpu(self.X, Q, kk, method=self.cpu_method)
+        return K.vote_curve_cpu(i, kk, self.y, kmax)[0]
+
+    def _loo_kmax(self, kmax):
+        kmax = int(kmax)
+        if not 1 <= kmax < K.VOTE_CURVE_KMAX:  # the search runs at kmax + 1: the row itself
+            raise ValueError(f"kmax must be in [1, {K.VOTE_CURVE_KMAX - 1}]")
+        return kmax
+
+    def _loo_batch(self, rows, kmax, lists, hits=None):
+        """Dataset rows `rows` (a slice with step 1, or an int array) as queries at k = min(kmax +
+        1, N), then the curve with skip = the row's own id: (labels, hits, lists), on the device
+        for a GPU.  With duplicates the row need not lead its own list, and when more than kmax +
+        1 points tie at distance 0 it may be absent: the first kmax entries are then the answer,
+        which is what dropping the id wherever it sits (or nowhere) gives."""
+        N = self.X.shape[0]
+        ks = max(1, min(kmax + 1, N))
+        if isinstance(rows, slice):
+            idx = np.arange(*rows.indices(N), dtype=np.int32)
+        else:
+            idx = np.ascontiguousarray(rows, np.int64)
+            if idx.ndim != 1 or (len(idx) and (idx.min() < -N or idx.max() >= N)):
+                raise ValueError("rows must be a slice or a 1-d array of row ids")
+            idx = np.where(idx < 0, idx + N, idx).astype(np.int32)
+        kk = np.full(len(idx), ks, np.int32)
+        if self.on_gpu:
+            torch = _torch()
+            ds = self._ds
+            if isinstance(rows, slice) and rows.indices(N)[2] == 1:
+                Qd = ds.X[idx[0]:idx[0] + len(idx)] if len(idx) else ds.X[:0]
+            else:  # a device-to-device gather: no host round trip
+                Qd = ds.X.index_select(0, torch.from_numpy(idx.astype(np.int64)).to(ds.X.device))
+            r = K.knn_gpu(ds, Qd, kk, finalize=False, exact=self.exact, kstride=ks)
+            me = torch.from_numpy(idx).to(ds.X.device)
+            return K.vote_curve_gpu(r.ids, kk, ds.labels, kmax, skip=me,
+                                    truth=ds.labels[me.long()] if not lists else None,
+                                    dist=r.dist if lists else None, hits=hits)
+        d, i = K.knn_cpu(self.X, self.X[idx], kk, kstride=ks, method=self.cpu_method)
+        return K.vote_curve_cpu(i, kk, self.y, kmax, skip=idx,
+                                truth=self.y[idx] if not lists else None,
+                                dist=d if lists else None, hits=hits)
+
+    def loo_kneighbors(self, kmax: int, rows=None):
+        """(dist, ids) [R, kmax]: the kmax nearest neighbours of the dataset rows `rows` (a slice
+        or an index array; default: all) with the row itself left out, padded with (+inf, -1)
+        when fewer than kmax other points exist.  kmax <= 255."""
+        kmax = self._loo_kmax(kmax)
+        _, _, (d, i) = self._loo_batch(slice(None) if rows is None else rows, kmax, lists=True)
+        if self.on_gpu:
+            return d.cpu().numpy(), i.cpu().numpy()
+        return d, i
+
+    def loo_curve(self, kmax: int, batch_rows: int = 65536):
+        """(hits int64 [kmax], N): hits[k - 1] = the rows whose k nearest OTHER rows vote their own
+        label — leave-one-out, every k <= kmax from one self-join in batches of batch_rows rows.
+        On a GPU the counts stay on the device over the batches: one copy back at the end."""
+        kmax = self._loo_kmax(kmax)
+        N = self.X.shape[0]
+        step = max(1, int(batch_rows))
+        hits = None
+        for a in range(0, N, step):
+            _, hits, _ = self._loo_batch(slice(a, min(N, a + step)), kmax, lists=False, hits=hits)
+        if hits is None:
+            return np.zeros(kmax, np.int64), N
+        return (hits.cpu().numpy() if self.on_gpu else hits), N
+
+    def select_k(self, kmax: int):
+        """(best_k, accuracy float64 [kmax]): leave-one-out accuracy of every k <= kmax and the
+        smallest k that reaches the best one (chosen on the integer hit counts)."""
+        hits, N = self.loo_curve(kmax)
+        if N == 0:
+            raise ValueError("select_k needs a fitted, non-empty dataset")
+        return int(np.argmax(hits)) + 1, hits.astype(np.float64) / N
 
 
 class KDTree:

@@ -10,7 +10,9 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            the screen's fp16 operands while the GPU screens (early start), the fp64 rows cross
            PCIe behind the screen as lossless int32, exact re-rank, vote, checksum, the report
            text rendered on the GPU into page-locked host memory, one host sync
-CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug).
+  vote_curve_gpu (dmlp_vote_curve)  the vote of every prefix of the sorted lists in one launch
+           (csrc/vote_curve.hip): the votes of all k <= kmax for one search, leave-one-out hit counts
+CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu.
 
 Exactness contract (common.cpp:57-79, engine.cpp:12-18): distances are the
 reference's left-to-right fp64 sums without FMA; the MFMA screens only filter candidates, with a
@@ -78,6 +80,48 @@ def finalize_cpu(ids: np.ndarray, k: np.ndarray, labels: np.ndarray):
                                             k.ctypes.data, Q, labels.ctypes.data,
                                             lab.ctypes.data, cs.ctypes.data), "cpu finalize")
     return lab, cs
+
+
+VOTE_CURVE_KMAX = 256   # dmlp_vote_curve_kmax(): slots of a list the curve kernels read
+
+
+def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
+    """The vote of every prefix of sorted lists (dmlp_cpu_vote_curve): ids [Q, kstride] int32, k
+    [Q], labels [N]; skip [Q] drops one id per row (negative: none), entries with id < 0 are
+    dropped too.  Returns (labels [Q, kcap] int32 — column j the vote over the first j + 1 kept
+    entries, repeated past the last one, -1 for an empty row —, hits int64 [kcap] | None — with
+    truth [Q]: rows whose column j equals truth, ADDED to `hits` when one is passed —, (dist, ids)
+    [Q, kcap] | None — with dist: the kept entries, padded with (+inf, -1))."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 2:
+        raise ValueError("ids must be [Q, kstride]")
+    Q, ks = ids.shape
+    k = np.ascontiguousarray(k, np.int32)
+    labels = np.ascontiguousarray(labels, np.int32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
+    truth = None if truth is None else np.ascontiguousarray(truth, np.int32)
+    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
+    if len(k) != Q or any(a is not None and len(a) != Q for a in (skip, truth)) or \
+            (dist is not None and dist.shape != ids.shape):
+        raise ValueError("k, skip, truth must be [Q] and dist shaped like ids")
+    kcap = int(kcap)
+    if not 1 <= kcap <= VOTE_CURVE_KMAX:
+        raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
+    lab = np.empty((Q, kcap), np.int32)
+    od = np.empty((Q, kcap), np.float64) if dist is not None else None
+    oi = np.empty((Q, kcap), np.int32) if dist is not None else None
+    if truth is not None:
+        if hits is None:
+            hits = np.zeros(kcap, np.int64)
+        elif hits.dtype != np.int64 or hits.shape != (kcap,) or not hits.flags.c_contiguous:
+            raise ValueError("hits must be a contiguous int64 [kcap] array")
+    else:
+        hits = None
+    _lib.check(_lib.lib().dmlp_cpu_vote_curve(
+        _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip), labels.ctypes.data,
+        kcap, lab.ctypes.data, _np_ptr(od), _np_ptr(oi), _np_ptr(truth), _np_ptr(hits)),
+        "cpu vote curve")
+    return lab, hits, ((od, oi) if dist is not None else None)
 
 
 def merge_cpu(lists_d: np.ndarray, lists_i: np.ndarray, k: np.ndarray, kout: int | None = None):
@@ -522,6 +566,49 @@ def finalize_gpu(ds_labels, label_range, dist, ids, k_dev):
                                         label_range[0], label_range[1], _p(lab), _p(cs),
                                         _stream()), "finalize")
     return lab, cs
+
+
+def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
+    """vote_curve_cpu on the device (dmlp_vote_curve, csrc/vote_curve.hip): ids [Q, kstride] int32,
+    k / skip / truth [Q] int32, labels [N] int32 and dist (shaped like ids, float64) are torch
+    tensors on one GPU (k may be a host array).  `hits`: an int64 [kcap] tensor there that the
+    counts are ADDED to (a fresh zeroed one when truth is given without it), so a caller can sum
+    over batches of rows without a copy back.  Asynchronous on the current stream."""
+    torch = _torch()
+    if ids.dim() != 2 or ids.dtype != torch.int32:
+        raise ValueError("ids must be an int32 [Q, kstride] tensor")
+    dev = ids.device
+    Q, ks = ids.shape
+    if not torch.is_tensor(k):
+        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
+
+    def i32(t):
+        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
+    ids, k, labels, skip, truth = ids.contiguous(), i32(k), i32(labels), i32(skip), i32(truth)
+    if dist is not None:
+        dist = dist.contiguous()
+        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
+            raise ValueError("dist must be a float64 tensor shaped like ids")
+    if k.numel() != Q or any(a is not None and a.numel() != Q for a in (skip, truth)):
+        raise ValueError("k, skip, truth must be [Q]")
+    kcap = int(kcap)
+    if not 1 <= kcap <= VOTE_CURVE_KMAX:
+        raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
+    lab = torch.empty((Q, kcap), dtype=torch.int32, device=dev)
+    od = torch.empty((Q, kcap), dtype=torch.float64, device=dev) if dist is not None else None
+    oi = torch.empty((Q, kcap), dtype=torch.int32, device=dev) if dist is not None else None
+    if truth is not None:
+        if hits is None:
+            hits = torch.zeros(kcap, dtype=torch.int64, device=dev)
+        elif hits.dtype != torch.int64 or tuple(hits.shape) != (kcap,) or hits.device != dev \
+                or not hits.is_contiguous():
+            raise ValueError("hits must be a contiguous int64 [kcap] tensor on the lists' device")
+    else:
+        hits = None
+    _lib.check(_lib.lib().dmlp_vote_curve(_p(dist), _p(ids), ks, _p(k), Q, _p(skip), _p(labels),
+                                          kcap, _p(lab), _p(od), _p(oi), _p(truth), _p(hits),
+                                          _stream()), "vote curve")
+    return lab, hits, ((od, oi) if dist is not None else None)
 
 
 # ---------------------------------------------------------------- report text on the GPU
