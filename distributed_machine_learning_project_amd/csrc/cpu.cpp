@@ -273,6 +273,55 @@ extern "C" int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride,
   return 0;
 }
 
+extern "C" int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk,
+                                    int64_t Q, const int* skip, const int* labels, int label_lo,
+                                    int nclass, int mode, int* out_count, double* out_score,
+                                    int* out_label) {
+  if (Q <= 0) return 0;
+  if (nclass < 1 || nclass > 4096 || kstride < 1 || mode < 0 || mode > 1) return -1;
+  if ((mode == 1 && !d) || (!out_count && !out_score && !out_label)) return -1;
+  std::vector<int> cnt((size_t)nclass), cls;
+  std::vector<double> sum((size_t)nclass), dk;
+  for (int64_t q = 0; q < Q; ++q) {
+    const int* iq = ids + q * kstride;
+    const int n = std::min(qk[q], kstride);
+    const int sk = skip ? skip[q] : -1;
+    cls.clear();
+    dk.clear();
+    bool zero = false;  // a kept entry at distance 0: the row's weights are 1 there, 0 elsewhere
+    for (int e = 0; e < n; ++e) {
+      const int id = iq[e];
+      if (id < 0 || id == sk) continue;
+      const int64_t c = (int64_t)labels[id] - label_lo;
+      if (c < 0 || c >= nclass) continue;
+      cls.push_back((int)c);
+      if (mode == 1) {
+        dk.push_back(d[q * kstride + e]);
+        zero |= dk.back() == 0.0;
+      }
+    }
+    std::fill(cnt.begin(), cnt.end(), 0);
+    std::fill(sum.begin(), sum.end(), 0.0);
+    for (size_t j = 0; j < cls.size(); ++j) {
+      const int c = cls[j];
+      ++cnt[c];
+      if (mode == 1) sum[c] = sum[c] + (zero ? (dk[j] == 0.0 ? 1.0 : 0.0) : 1.0 / dk[j]);
+    }
+    int best = -1;
+    for (int c = 0; c < nclass; ++c) {
+      if (mode == 0) sum[c] = (double)cnt[c];
+      if (out_count) out_count[q * nclass + c] = cnt[c];
+      if (out_score) out_score[q * nclass + c] = sum[c];
+      // (score, count, label) ascending in c: >= on a full tie takes the larger label
+      if (cnt[c] > 0 && (best < 0 || sum[c] > sum[best] ||
+                         (sum[c] == sum[best] && cnt[c] >= cnt[best])))
+        best = c;
+    }
+    if (out_label) out_label[q] = best < 0 ? -1 : (int)((int64_t)label_lo + best);
+  }
+  return 0;
+}
+
 extern "C" int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride,
                               int kin, const int* qk, int64_t Q, double* out_d, int* out_i,
                               int kout) {

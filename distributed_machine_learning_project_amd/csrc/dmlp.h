@@ -499,6 +499,30 @@ int dmlp_vote_curve(const double* d, const int* ids, int kstride, const int* qk,
                     const int* skip, const int* labels, int kcap, int* out_label, double* out_d,
                     int* out_i, const int* truth, unsigned long long* hits, void* stream);
 
+// ---- device: class scores (per-class vote counts and weighted votes of a neighbour list)
+// Row q < nq: slots e in [0, min(qk[q], kstride)) of ids[q * kstride ...] are read — the whole
+// list, no 256-slot clamp — and the same slots of d when mode == 1 (d may be null in mode 0).  An
+// entry is kept when ids[e] >= 0, ids[e] != skip[q] (skip nullable; a negative skip[q] excludes
+// nothing) and its label labels[ids[e]] lies in [label_lo, label_lo + nclass); kept entries keep
+// their list order, and a row with qk[q] <= 0 keeps nothing.
+//   out_count[q * nclass + c]: the kept entries with label label_lo + c (both modes).
+//   out_score[q * nclass + c] (nullable): mode 0 (uniform) (double)count; mode 1 (inverse SQUARED
+//     distance — d is the engine's squared L2 distance, no sqrt is taken) the sum of the class's
+//     weights w_e in list order, left to right, from 0.0, in fp64 without FMA: ((w_1 + w_2) + w_3)
+//     ...  w_e = 1.0 / d_e (IEEE division) when no kept entry of the row has d == 0; otherwise
+//     w_e = 1.0 where d_e == 0 and 0.0 elsewhere.  d = +inf weighs 0, a d whose inverse overflows
+//     weighs +inf.  d holds no NaN and no negative value.
+//   out_label[q] (nullable): among the classes with count > 0 the one with the largest (score,
+//     count, label), compared in that order; -1 when the row keeps nothing.  In mode 0 this is
+//     dmlp_finalize's vote (max count, ties -> larger label) and column k - 1 of the vote curve.
+// Every slot of the given outputs is written, nothing outside them.  nq <= 0 returns 0 and writes
+// nothing; nclass outside [1, dmlp_vote_scores_cmax()], kstride < 1, mode outside {0, 1}, mode 1
+// with a null d, or all three outputs null return -1 before any launch.
+int dmlp_vote_scores_cmax(void);  // 4096
+int dmlp_vote_scores(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                     const int* skip, const int* labels, int label_lo, int nclass, int mode,
+                     int* out_count, double* out_score, int* out_label, void* stream);
+
 // p[i] = v, i < n.  ids[i] += off where ids[i] >= 0 (0 included; the padding -1 is kept), i < n;
 // off = 0 launches nothing.  Nothing outside [0, n) is written.
 int dmlp_fill_f64(double* p, int64_t n, double v, void* stream);
@@ -532,6 +556,10 @@ int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stri
 int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                         const int* skip, const int* labels, int kcap, int* out_label,
                         double* out_d, int* out_i, const int* truth, unsigned long long* hits);
+// dmlp_vote_scores' contract on the host: a serial walk per row, bit-identical scores.
+int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
+                         const int* skip, const int* labels, int label_lo, int nclass, int mode,
+                         int* out_count, double* out_score, int* out_label);
 int dmlp_kdtree_knn(const double* X, int64_t N, int A, const double* Qx, int64_t Q,
                     const int* qk, int kstride, double* out_d, int* out_i);
 // Text report, host side.  Returns bytes written (buffer must hold 48*Q bytes).

@@ -4,6 +4,9 @@
     dist, ids = clf.kneighbors(Q, k)         # k: int or per-query array
     labels = clf.predict(Q, k)               # majority vote, ties -> larger label
     cs = clf.checksums(Q, k)                 # reference FNV-1a report checksums
+    proba = clf.predict_proba(Q, k)          # [Q, len(clf.classes_)]: class shares of the vote
+    proba = clf.predict_proba(Q, k, weights="inv_sqdist")   # neighbours weighted 1 / squared distance
+    labels = clf.predict(Q, k, weights="inv_sqdist")        # the weighted vote
     curve = clf.predict_curve(Q, kmax)       # [Q, kmax]: column k - 1 == predict(Q, k)
     dist, ids = clf.loo_kneighbors(kmax)     # neighbours of the dataset's own rows, self excluded
     hits, N = clf.loo_curve(kmax)            # leave-one-out hits of every k <= kmax
@@ -39,10 +42,11 @@ class KNNClassifier:
         self.y = np.ascontiguousarray(y, np.int32)
         if self.X.ndim != 2 or self.y.shape[0] != self.X.shape[0]:
             raise ValueError("X must be [N, A] and y [N]")
+        lo = int(self.y.min()) if len(self.y) else 0
+        hi = int(self.y.max()) + 1 if len(self.y) else 1
+        self._label_range = (lo, hi)
         if self.on_gpu:
             torch = _torch()
-            lo = int(self.y.min()) if len(self.y) else 0
-            hi = int(self.y.max()) + 1 if len(self.y) else 1
             self._ds = K.prepare_dataset(torch.from_numpy(self.X).cuda(),
                                          torch.from_numpy(self.y).cuda(), (lo, hi))
         return self
@@ -93,11 +97,57 @@ class KNNClassifier:
         d, i, _, _, _ = self._run(Q, k, finalize=False)
         return d, i
 
-    def predict(self, Q, k):
-        return self._run(Q, k, finalize=True)[2]
+    def predict(self, Q, k, weights: str = "uniform"):
+        """The vote of the k nearest neighbours.  weights="inv_sqdist": the class with the largest
+        (score, count, label) of predict_proba's weighted scores instead of the majority."""
+        if weights == "uniform":
+            return self._run(Q, k, finalize=True)[2]
+        return self._host(self._scores(Q, k, weights)[2])
 
     def checksums(self, Q, k):
         return self._run(Q, k, finalize=True)[3]
+
+    # ------------------------------------------------------------ class scores
+    # Per-class votes are a function of the lists the search leaves on the device: one search
+    # without the fused vote, then the class-score kernel (csrc/vote_scores.hip;
+    # dmlp_cpu_vote_scores on a CPU).
+    @property
+    def classes_(self):
+        """np.arange(lo, hi) over the fitted labels' range: the columns of predict_proba."""
+        lo, hi = self._label_range
+        if hi - lo > K.VOTE_SCORES_CMAX:
+            raise ValueError(f"the labels span {hi - lo} values: class scores take at most "
+                             f"{K.VOTE_SCORES_CMAX}")
+        return np.arange(lo, hi)
+
+    def _scores(self, Q, k, weights):
+        """(count [Q, C] int32, score [Q, C] float64, label [Q] int32) of the k nearest neighbours,
+        on the device for a GPU (_host brings one back)."""
+        if weights not in K.VOTE_WEIGHTS:
+            raise ValueError(f"weights must be one of {sorted(K.VOTE_WEIGHTS)}, not {weights!r}")
+        lo, nclass = int(self.classes_[0]), len(self.classes_)
+        Q = np.ascontiguousarray(Q, np.float64)
+        kk = self._k(Q, k)
+        if self.on_gpu:
+            torch = _torch()
+            r = K.knn_gpu(self._ds, torch.from_numpy(Q).cuda(), kk, finalize=False,
+                          exact=self.exact)
+            return K.vote_scores_gpu(r.ids, kk, self._ds.labels, lo, nclass, weights, dist=r.dist)
+        d, i = K.knn_cpu(self.X, Q, kk, method=self.cpu_method)
+        return K.vote_scores_cpu(i, kk, self.y, lo, nclass, weights, dist=d)
+
+    def _host(self, a):
+        return a.cpu().numpy() if self.on_gpu else a
+
+    def predict_proba(self, Q, k, weights: str = "uniform"):
+        """float64 [Q, len(classes_)]: the share of each class among the k nearest neighbours (k an
+        int or a per-query array).  weights="inv_sqdist" weighs a neighbour by 1 / d, d the
+        SQUARED distance the lists hold (not the 1 / distance of some libraries); a query that
+        coincides with training rows gives probability to their classes only.  Rows sum to 1; a
+        row without neighbours (k_q <= 0) is all zeros.  Bit-identical on both devices."""
+        cnt, sc, _ = self._scores(Q, k, weights)
+        # only the scores cross back, and the counts when a row's scores sum to 0
+        return K.class_proba(self._host(sc), lambda: self._host(cnt))
 
     # ------------------------------------------------------------ choosing k
     # The lists are sorted, so the vote for every k <= kmax is a function of one list: one search

@@ -1,3 +1,4 @@
 """Single-device compute ops: HIP kernels (GPU) and native host kernels (CPU)."""
 from .knn import (knn_cpu, finalize_cpu, merge_cpu, prepare_dataset, knn_gpu,  # noqa: F401
-                  merge_gpu, finalize_gpu, format_report_gpu, DeviceDataset, DeviceResult)
+                  merge_gpu, finalize_gpu, format_report_gpu, DeviceDataset, DeviceResult,
+                  vote_scores_cpu, vote_scores_gpu, class_proba, VOTE_SCORES_CMAX)

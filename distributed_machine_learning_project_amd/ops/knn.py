@@ -12,7 +12,10 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            text rendered on the GPU into page-locked host memory, one host sync
   vote_curve_gpu (dmlp_vote_curve)  the vote of every prefix of the sorted lists in one launch
            (csrc/vote_curve.hip): the votes of all k <= kmax for one search, leave-one-out hit counts
-CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu.
+  vote_scores_gpu (dmlp_vote_scores)  per-class vote counts and uniform / inverse-squared-distance
+           scores of the lists in one launch (csrc/vote_scores.hip): predict_proba, weighted predict
+CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu,
+vote_scores_cpu.
 
 Exactness contract (common.cpp:57-79, engine.cpp:12-18): distances are the
 reference's left-to-right fp64 sums without FMA; the MFMA screens only filter candidates, with a
@@ -122,6 +125,85 @@ def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
         kcap, lab.ctypes.data, _np_ptr(od), _np_ptr(oi), _np_ptr(truth), _np_ptr(hits)),
         "cpu vote curve")
     return lab, hits, ((od, oi) if dist is not None else None)
+
+
+VOTE_SCORES_CMAX = 4096  # dmlp_vote_scores_cmax(): classes a score launch takes
+VOTE_WEIGHTS = {"uniform": 0, "inv_sqdist": 1}  # the mode of dmlp_vote_scores
+
+
+def _score_mode(label_lo, nclass, weights, have_dist: bool):
+    """(label_lo, nclass, mode) of a class-score call, or ValueError for what the C entry rejects."""
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"weights must be one of {sorted(VOTE_WEIGHTS)}, not {weights!r}")
+    nclass = int(nclass)
+    if not 1 <= nclass <= VOTE_SCORES_CMAX:
+        raise ValueError(f"nclass must be in [1, {VOTE_SCORES_CMAX}]")
+    if VOTE_WEIGHTS[weights] == 1 and not have_dist:
+        raise ValueError("weights='inv_sqdist' needs dist")
+    label_lo = int(label_lo)
+    if not -(1 << 31) <= label_lo < (1 << 31):
+        raise ValueError("label_lo must be an int32")
+    return label_lo, nclass, VOTE_WEIGHTS[weights]
+
+
+def vote_scores_cpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "uniform",
+                    dist=None, skip=None):
+    """Per-class votes of neighbour lists (dmlp_cpu_vote_scores): ids [Q, kstride] int32, k [Q],
+    labels [N]; the first min(k_q, kstride) slots of a row are read, whatever their number; entries
+    with id < 0, with id == skip_q (skip [Q], negative: none) or with a label outside [label_lo,
+    label_lo + nclass) are dropped.  Returns (count [Q, nclass] int32, score [Q, nclass] float64,
+    label [Q] int32): weights="uniform" scores a class by its count; "inv_sqdist" by the sum, in
+    list order, of 1 / d over its entries (d: dist, shaped like ids, the engine's SQUARED distances;
+    a row with an entry at d == 0 counts those entries 1 and every other 0).  label is the class
+    with the largest (score, count, label), -1 for a row that keeps nothing."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 2 or ids.shape[1] < 1:
+        raise ValueError("ids must be [Q, kstride] with kstride >= 1")
+    Q, ks = ids.shape
+    label_lo, nclass, mode = _score_mode(label_lo, nclass, weights, dist is not None)
+    k = np.ascontiguousarray(k, np.int32)
+    labels = np.ascontiguousarray(labels, np.int32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
+    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
+    if k.shape != (Q,) or (skip is not None and skip.shape != (Q,)) or \
+            (dist is not None and dist.shape != ids.shape):
+        raise ValueError("k and skip must be [Q] and dist shaped like ids")
+    count = np.empty((Q, nclass), np.int32)
+    score = np.empty((Q, nclass), np.float64)
+    lab = np.empty(Q, np.int32)
+    _lib.check(_lib.lib().dmlp_cpu_vote_scores(
+        _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip), labels.ctypes.data,
+        label_lo, nclass, mode, count.ctypes.data, score.ctypes.data, lab.ctypes.data),
+        "cpu vote scores")
+    return count, score, lab
+
+
+def class_proba(score, count):
+    """Class probabilities [Q, C] float64 of the (score, count) a class-score call returned, as host
+    arrays — one function for both devices, so their probabilities agree bit for bit.  Per row:
+    score / total (total: the sum over classes); total == 0 (every neighbour at +inf): count / m
+    (m: the kept entries); no kept entry: zeros; a score at +inf: 1 / n_inf on those classes and 0
+    elsewhere.  `count` may be a callable returning the array: it is called only when a row's
+    scores sum to 0.  (Finite scores whose sum overflows are scaled by 2^-13 first, enough
+    for 4096 classes, rather than divided by +inf.)"""
+    score = np.ascontiguousarray(score, np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        total = score.sum(axis=1, keepdims=True)
+        inf = np.isinf(score)
+        has_inf = inf.any(axis=1, keepdims=True)
+        over = np.isinf(total) & ~has_inf
+        if over.any():
+            small = score * 2.0 ** -13
+            score = np.where(over, small, score)
+            total = np.where(over, small.sum(axis=1, keepdims=True), total)
+        p = score / total
+        p = np.where(has_inf, inf / inf.sum(axis=1, keepdims=True), p)
+        nothing = (total == 0).ravel()
+        if nothing.any():
+            cnt = np.asarray(count() if callable(count) else count)[nothing].astype(np.float64)
+            m = cnt.sum(axis=1, keepdims=True)
+            p[nothing] = np.where(m > 0, cnt / np.where(m > 0, m, 1.0), 0.0)
+    return p
 
 
 def merge_cpu(lists_d: np.ndarray, lists_i: np.ndarray, k: np.ndarray, kout: int | None = None):
@@ -609,6 +691,41 @@ def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
                                           kcap, _p(lab), _p(od), _p(oi), _p(truth), _p(hits),
                                           _stream()), "vote curve")
     return lab, hits, ((od, oi) if dist is not None else None)
+
+
+def vote_scores_gpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "uniform",
+                    dist=None, skip=None):
+    """vote_scores_cpu on the device (dmlp_vote_scores, csrc/vote_scores.hip): ids [Q, kstride]
+    int32, k / skip [Q] int32, labels [N] int32 and dist (shaped like ids, float64) are torch
+    tensors on one GPU (k may be a host array).  Returns (count [Q, nclass] int32, score [Q,
+    nclass] float64, label [Q] int32) there, bit-identical to the CPU's.  Asynchronous on the
+    current stream."""
+    torch = _torch()
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
+        raise ValueError("ids must be an int32 [Q, kstride] tensor with kstride >= 1")
+    dev = ids.device
+    Q, ks = ids.shape
+    label_lo, nclass, mode = _score_mode(label_lo, nclass, weights, dist is not None)
+    if not torch.is_tensor(k):
+        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
+
+    def i32(t):
+        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
+    ids, k, labels, skip = ids.contiguous(), i32(k), i32(labels), i32(skip)
+    if dist is not None:
+        dist = dist.contiguous()
+        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
+            raise ValueError("dist must be a float64 tensor shaped like ids")
+    if tuple(k.shape) != (Q,) or (skip is not None and tuple(skip.shape) != (Q,)):
+        raise ValueError("k and skip must be [Q]")
+    # every slot is written: no fill pass
+    count = torch.empty((Q, nclass), dtype=torch.int32, device=dev)
+    score = torch.empty((Q, nclass), dtype=torch.float64, device=dev)
+    lab = torch.empty(Q, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().dmlp_vote_scores(_p(dist), _p(ids), ks, _p(k), Q, _p(skip), _p(labels),
+                                           label_lo, nclass, mode, _p(count), _p(score), _p(lab),
+                                           _stream()), "vote scores")
+    return count, score, lab
 
 
 # ---------------------------------------------------------------- report text on the GPU
