@@ -124,6 +124,11 @@ _SIGS = {
     "dmlp_vote_scores_cmax": (i32, []),
     "dmlp_vote_scores": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dmlp_cpu_vote_scores": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "dmlp_neighbor_means_tmax": (i32, []),
+    "dmlp_neighbor_means": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "dmlp_neighbor_means_curve": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "dmlp_cpu_neighbor_means": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, i32, vp, vp, vp]),
+    "dmlp_cpu_neighbor_means_curve": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp]),
     "dmlp_format_bound": (i64, [i32]),
     "dmlp_format_scratch": (i64, [i32]),
     "dmlp_format_report": (i32, [vp, i32, i32, vp, vp, vp]),

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <thread>
 #include <unordered_map>
@@ -320,6 +321,79 @@ extern "C" int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride
     if (out_label) out_label[q] = best < 0 ? -1 : (int)((int64_t)label_lo + best);
   }
   return 0;
+}
+
+// Both neighbour-mean entry points (dmlp.h): a serial walk per row.  kcap == 0: the whole list
+// (out_wsum / out_count nullable); kcap >= 1: the curve, 256 slots read at most.
+static int neighbor_means(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
+                          const int* skip, const double* targets, int T, int mode, int kcap,
+                          bool curve, double* out_mean, double* out_wsum, int* out_count) {
+  if (Q <= 0) return 0;
+  if (T < 1 || T > 256 || kstride < 1 || mode < 0 || mode > 1) return -1;
+  if (curve && (kcap < 1 || kcap > 256)) return -1;
+  if ((mode == 1 && !d) || !out_mean || !ids || !qk || !targets) return -1;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> sum((size_t)T);
+  for (int64_t q = 0; q < Q; ++q) {
+    const int* iq = ids + q * kstride;
+    int n = std::min(qk[q], kstride);
+    if (curve) n = std::min(n, 256);
+    const int sk = skip ? skip[q] : -1;
+    std::fill(sum.begin(), sum.end(), 0.0);
+    double wsum = 0.0, dref = 1.0;
+    int m = 0;
+    for (int e = 0; e < n && (!curve || m < kcap); ++e) {
+      const int id = iq[e];
+      if (id < 0 || id == sk) continue;
+      const double* row = targets + (int64_t)id * T;
+      double w = 1.0;
+      if (mode == 1) {
+        const double x = d[q * kstride + e];
+        if (m == 0) dref = x;  // the first kept entry
+        w = dref == 0.0 ? (x == 0.0 ? 1.0 : 0.0) : dref == INFINITY ? 1.0 : dref / x;
+        for (int t = 0; t < T; ++t) {
+          const double p = w * row[t];
+          sum[t] = sum[t] + p;
+        }
+        wsum = wsum + w;
+      } else {
+        for (int t = 0; t < T; ++t) sum[t] = sum[t] + row[t];
+        wsum = (double)(m + 1);
+      }
+      if (curve) {
+        double* o = out_mean + (q * kcap + m) * T;
+        for (int t = 0; t < T; ++t) o[t] = sum[t] / wsum;
+      }
+      ++m;
+    }
+    if (curve) {
+      for (int j = m; j < kcap; ++j) {
+        double* o = out_mean + (q * kcap + j) * T;
+        for (int t = 0; t < T; ++t) o[t] = m ? o[t - T] : nan;
+      }
+    } else {
+      for (int t = 0; t < T; ++t) out_mean[q * T + t] = m ? sum[t] / wsum : nan;
+      if (out_wsum) out_wsum[q] = wsum;
+      if (out_count) out_count[q] = m;
+    }
+  }
+  return 0;
+}
+
+extern "C" int dmlp_cpu_neighbor_means(const double* d, const int* ids, int kstride, const int* qk,
+                                       int64_t Q, const int* skip, const double* targets, int T,
+                                       int mode, double* out_mean, double* out_wsum,
+                                       int* out_count) {
+  return neighbor_means(d, ids, kstride, qk, Q, skip, targets, T, mode, 0, false, out_mean,
+                        out_wsum, out_count);
+}
+
+extern "C" int dmlp_cpu_neighbor_means_curve(const double* d, const int* ids, int kstride,
+                                             const int* qk, int64_t Q, const int* skip,
+                                             const double* targets, int T, int mode, int kcap,
+                                             double* out_mean) {
+  return neighbor_means(d, ids, kstride, qk, Q, skip, targets, T, mode, kcap, true, out_mean,
+                        nullptr, nullptr);
 }
 
 extern "C" int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride,

@@ -523,6 +523,43 @@ int dmlp_vote_scores(const double* d, const int* ids, int kstride, const int* qk
                      const int* skip, const int* labels, int label_lo, int nclass, int mode,
                      int* out_count, double* out_score, int* out_label, void* stream);
 
+// ---- device: neighbour means (the weighted mean of the targets of a neighbour list, and of every
+// prefix of it)
+// targets is [N][T] row-major fp64 and finite.  Row q < nq: slots e in [0, min(qk[q], kstride)) of
+// ids[q * kstride ...] are read — the whole list; the curve form additionally clamps to 256 slots,
+// like dmlp_vote_curve — and the same slots of d when mode == 1 (d may be null in mode 0).  An
+// entry is kept when ids[e] >= 0 and ids[e] != skip[q] (skip nullable; a negative skip[q] excludes
+// nothing); kept entries keep their list order, m is their number, and a row with qk[q] <= 0 keeps
+// nothing.
+//   weights: mode 0 (uniform) w_e = 1.  mode 1 (inverse SQUARED distance — d is the engine's
+//     squared L2 distance, no sqrt is taken): d_ref is the distance of the FIRST kept entry (the
+//     lists are ascending, so the smallest; an unsorted list is the caller's problem and gets no
+//     check) and w_e = d_ref / d_e (IEEE division), so weights lie in [0, 1] and nothing overflows;
+//     d_ref == 0: w_e = 1.0 where d_e == 0 and 0.0 elsewhere; d_ref == +inf: every w_e = 1.0.
+//     The mean is that of 1 / d_e weights; the weights do not depend on the length of a prefix,
+//     so the curve's columns are true prefixes.  d holds no NaN and no negative value.
+//   sums: fp64, left to right from 0.0, without FMA: sum_t = ((p_1 + p_2) + p_3) ... with p_e =
+//     w_e * targets[id_e][t] (the product rounded, then the add; no multiply in mode 0), wsum =
+//     ((w_1 + w_2) + ...) (mode 0: (double)m), mean_t = sum_t / wsum (IEEE division; m >= 1 gives
+//     wsum >= 1).
+//   dmlp_neighbor_means: out_mean[q * T + t]; out_wsum[q] (nullable); out_count[q] = m (nullable).
+//     A row with m == 0 gets NaN means, wsum 0.0 and count 0.
+//   dmlp_neighbor_means_curve: out_mean[(q * kcap + j) * T + t], j < min(m, kcap): the mean over
+//     the first j + 1 kept entries; later j repeat the last computed slot; all NaN when m == 0.
+// Every slot of a given output is written, nothing outside it.  nq <= 0 returns 0 and writes
+// nothing; T outside [1, dmlp_neighbor_means_tmax()], kstride < 1, mode outside {0, 1}, mode 1 with
+// a null d, kcap outside [1, 256] or a null out_mean, ids, qk or targets return -1 before any
+// launch.  Results that are not NaN are bit-identical to the host twins'; where the contract yields
+// NaN (an empty row, inf - inf from overflowing targets) both yield a NaN, whose payload is not
+// part of the contract.
+int dmlp_neighbor_means_tmax(void);   // 256
+int dmlp_neighbor_means(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                        const int* skip, const double* targets, int T, int mode,
+                        double* out_mean, double* out_wsum, int* out_count, void* stream);
+int dmlp_neighbor_means_curve(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                              const int* skip, const double* targets, int T, int mode, int kcap,
+                              double* out_mean, void* stream);
+
 // p[i] = v, i < n.  ids[i] += off where ids[i] >= 0 (0 included; the padding -1 is kept), i < n;
 // off = 0 launches nothing.  Nothing outside [0, n) is written.
 int dmlp_fill_f64(double* p, int64_t n, double v, void* stream);
@@ -560,6 +597,14 @@ int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int*
 int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                          const int* skip, const int* labels, int label_lo, int nclass, int mode,
                          int* out_count, double* out_score, int* out_label);
+// dmlp_neighbor_means' and dmlp_neighbor_means_curve's contracts on the host: a serial walk per
+// row, the same argument checks, bit-identical means.
+int dmlp_cpu_neighbor_means(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
+                            const int* skip, const double* targets, int T, int mode,
+                            double* out_mean, double* out_wsum, int* out_count);
+int dmlp_cpu_neighbor_means_curve(const double* d, const int* ids, int kstride, const int* qk,
+                                  int64_t Q, const int* skip, const double* targets, int T,
+                                  int mode, int kcap, double* out_mean);
 int dmlp_kdtree_knn(const double* X, int64_t N, int A, const double* Qx, int64_t Q,
                     const int* qk, int kstride, double* out_d, int* out_i);
 // Text report, host side.  Returns bytes written (buffer must hold 48*Q bytes).

@@ -1,2 +1,3 @@
-"""Model front-ends (exact k-NN classifier, serial KD-tree)."""
+"""Model front-ends (exact k-NN classifier and regressor, serial KD-tree)."""
 from .knn_classifier import KDTree, KNNClassifier  # noqa: F401
+from .knn_regressor import KNNRegressor  # noqa: F401

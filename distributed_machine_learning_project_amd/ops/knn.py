@@ -14,8 +14,13 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            (csrc/vote_curve.hip): the votes of all k <= kmax for one search, leave-one-out hit counts
   vote_scores_gpu (dmlp_vote_scores)  per-class vote counts and uniform / inverse-squared-distance
            scores of the lists in one launch (csrc/vote_scores.hip): predict_proba, weighted predict
+  neighbor_means_gpu / neighbor_means_curve_gpu (dmlp_neighbor_means, dmlp_neighbor_means_curve)
+           the uniform / inverse-squared-distance mean of the neighbours' float targets, for the
+           whole list or for every prefix of it, in one launch (csrc/neighbor_means.hip):
+           KNNRegressor's predict, predict_curve and leave-one-out curves
 CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu,
-vote_scores_cpu.
+vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu.  curve_sse (host, both devices)
+turns a mean curve into squared errors.
 
 Exactness contract (common.cpp:57-79, engine.cpp:12-18): distances are the
 reference's left-to-right fp64 sums without FMA; the MFMA screens only filter candidates, with a
@@ -204,6 +209,91 @@ def class_proba(score, count):
             m = cnt.sum(axis=1, keepdims=True)
             p[nothing] = np.where(m > 0, cnt / np.where(m > 0, m, 1.0), 0.0)
     return p
+
+
+NEIGHBOR_MEANS_TMAX = 256  # dmlp_neighbor_means_tmax(): target columns a mean launch takes
+
+
+def _means_args(T, weights, have_dist: bool, kcap=None):
+    """(T, mode, kcap) of a neighbour-mean call, or ValueError for what the C entry rejects."""
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"weights must be one of {sorted(VOTE_WEIGHTS)}, not {weights!r}")
+    if not 1 <= T <= NEIGHBOR_MEANS_TMAX:
+        raise ValueError(f"targets must have between 1 and {NEIGHBOR_MEANS_TMAX} columns")
+    if VOTE_WEIGHTS[weights] == 1 and not have_dist:
+        raise ValueError("weights='inv_sqdist' needs dist")
+    if kcap is not None:
+        kcap = int(kcap)
+        if not 1 <= kcap <= VOTE_CURVE_KMAX:
+            raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
+    return int(T), VOTE_WEIGHTS[weights], kcap
+
+
+def _means_cpu_args(ids, k, targets, weights, dist, skip, kcap=None):
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 2 or ids.shape[1] < 1:
+        raise ValueError("ids must be [Q, kstride] with kstride >= 1")
+    Q = ids.shape[0]
+    targets = np.ascontiguousarray(targets, np.float64)
+    if targets.ndim != 2:
+        raise ValueError("targets must be [N, T]")
+    T, mode, kcap = _means_args(targets.shape[1], weights, dist is not None, kcap)
+    k = np.ascontiguousarray(k, np.int32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
+    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
+    if k.shape != (Q,) or (skip is not None and skip.shape != (Q,)) or \
+            (dist is not None and dist.shape != ids.shape):
+        raise ValueError("k and skip must be [Q] and dist shaped like ids")
+    return ids, k, targets, dist, skip, T, mode, kcap
+
+
+def neighbor_means_cpu(ids, k, targets, weights: str = "uniform", dist=None, skip=None):
+    """The mean of the neighbours' targets (dmlp_cpu_neighbor_means): ids [Q, kstride] int32, k
+    [Q], targets [N, T] float64, finite; the first min(k_q, kstride) slots of a row are read,
+    whatever their number; entries with id < 0 or id == skip_q (skip [Q], negative: none) are
+    dropped.  Returns (mean [Q, T] float64, wsum [Q] float64, count [Q] int32): weights="uniform"
+    is the plain mean; "inv_sqdist" weighs an entry by d_ref / d (dist, shaped like ids, the
+    engine's SQUARED distances; d_ref the first kept entry's), which is the mean under 1 / d
+    weights: a row whose first kept entry sits at d == 0 averages its entries at d == 0 only.
+    Sums run in list order, left to right, without FMA; a row that keeps nothing is NaN with wsum
+    0 and count 0."""
+    ids, k, targets, dist, skip, T, mode, _ = _means_cpu_args(ids, k, targets, weights, dist, skip)
+    Q, ks = ids.shape
+    mean = np.empty((Q, T), np.float64)
+    wsum = np.empty(Q, np.float64)
+    count = np.empty(Q, np.int32)
+    _lib.check(_lib.lib().dmlp_cpu_neighbor_means(
+        _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip), targets.ctypes.data,
+        T, mode, mean.ctypes.data, wsum.ctypes.data, count.ctypes.data), "cpu neighbor means")
+    return mean, wsum, count
+
+
+def neighbor_means_curve_cpu(ids, k, targets, kcap: int, weights: str = "uniform", dist=None,
+                             skip=None):
+    """The mean over every prefix of the lists (dmlp_cpu_neighbor_means_curve): float64 [Q, kcap,
+    T], column j the mean over the first j + 1 kept entries of the first min(k_q, kstride, 256)
+    slots — neighbor_means_cpu at that length, bit for bit —, repeated past the last kept entry,
+    NaN for a row that keeps nothing.  Arguments as for neighbor_means_cpu."""
+    ids, k, targets, dist, skip, T, mode, kcap = _means_cpu_args(ids, k, targets, weights, dist,
+                                                                 skip, kcap)
+    Q, ks = ids.shape
+    mean = np.empty((Q, kcap, T), np.float64)
+    _lib.check(_lib.lib().dmlp_cpu_neighbor_means_curve(
+        _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip), targets.ctypes.data,
+        T, mode, kcap, mean.ctypes.data), "cpu neighbor means curve")
+    return mean
+
+
+def curve_sse(mean, truth):
+    """float64 [kcap, T]: the squared error of every column of a mean curve, summed over the rows
+    — ((mean - truth[:, None, :]) ** 2).sum(axis=0) for mean [R, kcap, T] and truth [R, T], as host
+    arrays.  One function for both devices, so their leave-one-out errors agree bit for bit."""
+    mean = np.ascontiguousarray(mean, np.float64)
+    truth = np.ascontiguousarray(truth, np.float64)
+    if mean.ndim != 3 or truth.shape != (mean.shape[0], mean.shape[2]):
+        raise ValueError("mean must be [R, kcap, T] and truth [R, T]")
+    with np.errstate(over="ignore", invalid="ignore"):
+        return ((mean - truth[:, None, :]) ** 2).sum(axis=0)
 
 
 def merge_cpu(lists_d: np.ndarray, lists_i: np.ndarray, k: np.ndarray, kout: int | None = None):
@@ -726,6 +816,66 @@ def vote_scores_gpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "
                                            label_lo, nclass, mode, _p(count), _p(score), _p(lab),
                                            _stream()), "vote scores")
     return count, score, lab
+
+
+def _means_gpu_args(ids, k, targets, weights, dist, skip, kcap=None):
+    torch = _torch()
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
+        raise ValueError("ids must be an int32 [Q, kstride] tensor with kstride >= 1")
+    dev = ids.device
+    Q = ids.shape[0]
+    if targets.dim() != 2 or targets.dtype != torch.float64 or targets.device != dev:
+        raise ValueError("targets must be a float64 [N, T] tensor on the lists' device")
+    T, mode, kcap = _means_args(targets.shape[1], weights, dist is not None, kcap)
+    if not torch.is_tensor(k):
+        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
+
+    def i32(t):
+        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
+    ids, k, skip, targets = ids.contiguous(), i32(k), i32(skip), targets.contiguous()
+    if dist is not None:
+        dist = dist.contiguous()
+        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
+            raise ValueError("dist must be a float64 tensor shaped like ids")
+    if tuple(k.shape) != (Q,) or (skip is not None and tuple(skip.shape) != (Q,)):
+        raise ValueError("k and skip must be [Q]")
+    return ids, k, targets, dist, skip, T, mode, kcap
+
+
+def neighbor_means_gpu(ids, k, targets, weights: str = "uniform", dist=None, skip=None):
+    """neighbor_means_cpu on the device (dmlp_neighbor_means, csrc/neighbor_means.hip): ids [Q,
+    kstride] int32, k / skip [Q] int32, targets [N, T] float64 and dist (shaped like ids, float64)
+    are torch tensors on one GPU (k may be a host array).  Returns (mean [Q, T] float64, wsum [Q]
+    float64, count [Q] int32) there, bit-identical to the CPU's.  Asynchronous on the current
+    stream."""
+    torch = _torch()
+    ids, k, targets, dist, skip, T, mode, _ = _means_gpu_args(ids, k, targets, weights, dist, skip)
+    Q, ks = ids.shape
+    dev = ids.device
+    # every slot is written: no fill pass
+    mean = torch.empty((Q, T), dtype=torch.float64, device=dev)
+    wsum = torch.empty(Q, dtype=torch.float64, device=dev)
+    count = torch.empty(Q, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().dmlp_neighbor_means(_p(dist), _p(ids), ks, _p(k), Q, _p(skip),
+                                              _p(targets), T, mode, _p(mean), _p(wsum), _p(count),
+                                              _stream()), "neighbor means")
+    return mean, wsum, count
+
+
+def neighbor_means_curve_gpu(ids, k, targets, kcap: int, weights: str = "uniform", dist=None,
+                             skip=None):
+    """neighbor_means_curve_cpu on the device (dmlp_neighbor_means_curve): the mean over every
+    prefix of the lists in one launch, float64 [Q, kcap, T] on the lists' GPU, bit-identical to the
+    CPU's.  Arguments as for neighbor_means_gpu.  Asynchronous on the current stream."""
+    torch = _torch()
+    ids, k, targets, dist, skip, T, mode, kcap = _means_gpu_args(ids, k, targets, weights, dist,
+                                                                 skip, kcap)
+    Q, ks = ids.shape
+    mean = torch.empty((Q, kcap, T), dtype=torch.float64, device=ids.device)
+    _lib.check(_lib.lib().dmlp_neighbor_means_curve(_p(dist), _p(ids), ks, _p(k), Q, _p(skip),
+                                                    _p(targets), T, mode, kcap, _p(mean),
+                                                    _stream()), "neighbor means curve")
+    return mean
 
 
 # ---------------------------------------------------------------- report text on the GPU
