@@ -149,6 +149,17 @@ int dmlp_host_ops_h2d_tiles(const double* X, int64_t N, int64_t t0, int64_t t1, 
                             float* xin_h, unsigned* xnm_h, uint16_t* qhi_h, float* qn_h,
                             void* xhi_d, void* xin_d, void* xnm_d, void* qhi_d, void* qn_d,
                             int chunks, void* stream);
+// Either of the two above (Xr / Qr non-null: the row tables) for a caller whose query operands
+// are ONE allocation each, in staging and on the device: the Q fragments, then the Q norms
+// directly behind them (qn_h == qhi_h + Q KT 32 and qn_d == qhi_d + Q KT 64 bytes).  q_joined != 0
+// states that layout: every query chunk is then one copy, and the last chunk's copy runs on
+// through all the norms (chunks copies instead of 2 chunks).  q_joined == 0: the copies above.
+int dmlp_host_ops_h2d_tiles_q(const double* X, const double* const* Xr, int64_t N, int64_t t0,
+                              int64_t t1, const double* Qx, const double* const* Qr, int64_t Q,
+                              int A, const double* mu, int KT, uint16_t* xhi_h, float* xin_h,
+                              unsigned* xnm_h, uint16_t* qhi_h, float* qn_h, void* xhi_d,
+                              void* xin_d, void* xnm_d, void* qhi_d, void* qn_d, int chunks,
+                              int q_joined, void* stream);
 
 // ---------------------------------------------------------------- device: screen (K2+K3, fused)
 // bf16x3 MFMA screen + per-query streaming threshold + candidate compaction.  Queries are the
@@ -230,6 +241,13 @@ int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, const float* x
                         const int* qidx, const int* qk, int nq, int kmax,
                         const unsigned* xnmax_bits, const unsigned* bad, int S, int s_first,
                         int S_l, int* cand_ids, int* cand_cnt, float* cand_h, void* stream);
+// ... with a uniform k as a scalar: kuni >= 0 is every query's k (qk is not read and may still be
+// in flight or null; kuni <= kmax), kuni < 0 reads qk[q] like the entry above
+int dmlp_screen_x1_part_k(int KT, int hl, int A, const void* xfrag, const float* xinit,
+                          int64_t n_tiles, int64_t n_points, const void* qhi, const float* qn,
+                          const int* qidx, const int* qk, int kuni, int nq, int kmax,
+                          const unsigned* xnmax_bits, const unsigned* bad, int S, int s_first,
+                          int S_l, int* cand_ids, int* cand_cnt, float* cand_h, void* stream);
 // Profiling / tuning switches (process-wide): ablation mode, 4-row group appends on/off,
 // sub-buffer depth (8 / 16, 0 = automatic).
 void dmlp_set_stream_mode(int mode);
@@ -307,6 +325,12 @@ int dmlp_screen_x1_early(int KT, int A, const void* xfrag, const float* xinit, i
                          const int* qk, int nq, int kmax, const unsigned* bad, const unsigned* rdy,
                          int rdy_tiles, int rdy_n, int* cand_ids, int* cand_cnt, float* cand_h,
                          unsigned* estats, void* stream);
+// (kuni: as dmlp_screen_x1_part_k)
+int dmlp_screen_x1_early_k(int KT, int A, const void* xfrag, const float* xinit, int64_t n_tiles,
+                           int64_t n_points, const void* qhi, const float* qn, const int* qidx,
+                           const int* qk, int kuni, int nq, int kmax, const unsigned* bad,
+                           const unsigned* rdy, int rdy_tiles, int rdy_n, int* cand_ids,
+                           int* cand_cnt, float* cand_h, unsigned* estats, void* stream);
 
 // ---------------------------------------------------------------- node render plane (plane.cpp)
 // P ranks of a node stepping against ONE dataset render it once: slice i of the dataset (image

@@ -44,12 +44,15 @@ struct Local {
   I32Rows* i32 = nullptr;  // (dmlp_step) rows still int32 on the device, or none
   // (dmlp_step) k already clamped to N and on the device (kd_pre), every k in [1, 64] and <= N
   // (all_a_pre), the overflow counter zeroed on the device (ovf_pre): no host pass over the
-  // queries and no copy or memset on `st` between the operands' event and the screen
+  // queries and no copy or memset on `st` between the operands' event and the screen.
+  // kuni_pre >= 0: every k is this value — the all-queries screen takes it as a scalar and kd_pre
+  // may still be crossing PCIe on the stream whose `rows` event the refine waits for
   const int* kk_pre = nullptr;
   int* kd_pre = nullptr;
   int* ovf_pre = nullptr;
   bool all_a_pre = false;
   int kmax_pre = 0;
+  int kuni_pre = -1;
   // state
   int* kk = nullptr;
   int* kd = nullptr;
@@ -140,23 +143,24 @@ struct Local {
       const void* qh = hx ? hx->qhi : (const void*)w.qhi.p;
       const float* qnn = hx ? hx->qn : w.qn.p;
       const int hl = hx ? 1 : 2;
+      const int kuni = !idx && kd == kd_pre ? kuni_pre : -1;  // (kd_pre: not landed before rows)
       if (hx && hx->rdy) {
         // the caller sized the early start for this all-queries pass with one slice
         if (S != 1 || idx) throw Fail{-7};
-        CKL(dmlp_screen_x1_early(KT, A, xf, xi, nt, N, qh, qnn, qi, kd, nq, kcls, wd + 1, hx->rdy,
-                                 hx->rdy_tiles, hx->rdy_n, ci, cc, ch, hx->estats, st));
+        CKL(dmlp_screen_x1_early_k(KT, A, xf, xi, nt, N, qh, qnn, qi, kd, kuni, nq, kcls, wd + 1,
+                                   hx->rdy, hx->rdy_tiles, hx->rdy_n, ci, cc, ch, hx->estats, st));
       } else if (hx && hx->chunk_n > 0 && !idx) {
         // the large-N pipeline: each chunk's slices as soon as its rows are rendered
         for (int c = 0; c < hx->chunk_n; ++c) {
           hx->issue_chunk(c);  // (the host packs chunk c + 1 while chunk c's screen runs)
           CK(hipStreamWaitEvent(st, hx->chunk_ev[c], 0));
-          CKL(dmlp_screen_x1_part(KT, hl, A, xf, xi, nt, N, qh, qnn, qi, kd, nq, kcls, wd, wd + 1,
-                                  S, hx->chunk_s[c], hx->chunk_s[c + 1] - hx->chunk_s[c], ci, cc,
-                                  ch, st));
+          CKL(dmlp_screen_x1_part_k(KT, hl, A, xf, xi, nt, N, qh, qnn, qi, kd, kuni, nq, kcls, wd,
+                                    wd + 1, S, hx->chunk_s[c], hx->chunk_s[c + 1] - hx->chunk_s[c],
+                                    ci, cc, ch, st));
         }
       } else {
-        CKL(dmlp_screen_x1(KT, hl, A, xf, xi, nt, N, qh, qnn, qi, kd, nq, kcls, wd, wd + 1, S, ci,
-                           cc, ch, st));
+        CKL(dmlp_screen_x1_part_k(KT, hl, A, xf, xi, nt, N, qh, qnn, qi, kd, kuni, nq, kcls, wd,
+                                  wd + 1, S, 0, S, ci, cc, ch, st));
       }
       // (issues the row copies first) the re-rank reads the rows: the pair refine as int32 when
       // they crossed that way, the others as fp64

@@ -47,10 +47,13 @@
 namespace dmlp_pipe {
 
 // The step's small results in one word block: [0] report length, [1] overflowed queries,
-// [2..4] early-start waits / eps growths / timeouts.
-__global__ void k_pack_small(const int64_t* __restrict__ len, const int* __restrict__ ovf,
-                             const unsigned* __restrict__ estats, const unsigned* __restrict__ rbad,
-                             int64_t* __restrict__ out) {
+// [2..4] early-start waits / eps growths / timeouts.  Then the step's words (clear[0, nclear),
+// nclear <= the block; ovf and estats lie among them) zeroed for the next call: every reader and
+// writer of them precedes this kernel on its stream, so the next call needs no zero copy in
+// front of its operands.  (ovf / estats are not __restrict__: they alias clear.)
+__global__ void k_pack_small(const int64_t* __restrict__ len, const int* ovf,
+                             const unsigned* estats, const unsigned* __restrict__ rbad,
+                             int64_t* __restrict__ out, unsigned* clear, int nclear) {
   if (threadIdx.x == 0) {
     out[0] = len ? *len : 0;
     out[1] = *ovf;
@@ -60,6 +63,8 @@ __global__ void k_pack_small(const int64_t* __restrict__ len, const int* __restr
     out[5] = estats ? estats[3] : 0;
     out[6] = rbad ? *rbad : 0;
   }
+  __syncthreads();  // (the reads above before any store below)
+  if ((int)threadIdx.x < nclear) clear[threadIdx.x] = 0u;
 }
 
 // Keep one wave per CU busy for `us` microseconds of the constant-rate wall clock (tick_khz
@@ -289,6 +294,10 @@ struct Step {
     int* kh = front_sure && Q > 0 ? w.kk_h.get(Q) : nullptr;
     double* mu = front_sure ? w.s_mu.get(A) : nullptr;
     unsigned* words = w.dwords.get(kW_N);
+    // the words are zero already when the previous call's tail cleared them (k_pack_small) and
+    // this is still that buffer; not vouched for again until this call's own tail has run
+    const bool words_clean = w.words_clean == words;
+    w.words_clean = nullptr;
     struct Prelude {  // (a throw between begin and end must not leave the pool's workers taken)
       bool open = false;
       int end(int* k0, int* k1, int* l0, int* l1) {
@@ -308,10 +317,11 @@ struct Step {
     // copies into them start after it
     CK(hipEventRecord(w.ev_ops, st));
     CK(hipStreamWaitEvent(w.side, w.ev_ops, 0));
-    // the step's words (norm, bad, ready words, counters, overflow) zeroed by one DMA copy on the
-    // side stream ahead of the operands, so nothing sits on `st` between the operands' event and
-    // the screen
-    if (Q > 0) CK(dma_zero(words, kW_N * sizeof(unsigned), w.side));
+    // the step's words (norm, bad, ready words, counters, overflow) must be zero: the previous
+    // call's tail left them so (words_clean), else one DMA copy on the side stream ahead of the
+    // operands (a first call, or one after a call that returned early or failed) — either way
+    // nothing sits on `st` between the operands' event and the screen
+    if (Q > 0 && !words_clean) CK(dma_zero(words, kW_N * sizeof(unsigned), w.side));
     int kmin = a->kmin, kmax = a->kmax, lmin = 0, lmax = -1;
     if (pre.end(&kmin, &kmax, &lmin, &lmax) != 0) return -1;
     if (scan_k) {  // k bounds not given
@@ -374,16 +384,22 @@ struct Step {
     unsigned* estats = words + kW_EST;
     HostOps hx;
     bool use_hx = false, early_bad = false;
-    // ---- on the all-class-a path k on the device, on the side stream ahead of the operands like
-    // the words' zero copy (the prelude staged it, unless the front was not sure by then)
+    // ---- on the all-class-a path k on the device (the prelude staged it, unless the front was
+    // not sure by then).  Mixed k: on the side stream ahead of the operands, the screen reads it.
+    // Uniform k (kmin == kmax, given or scanned): the screen takes the scalar, and the array —
+    // the refine's — is copied behind the operands' event, off the screen's critical path (the
+    // refine waits for the rows' event, recorded on that stream after it).  Not under the device
+    // render, whose one-chunk form records the rows' event before the operands' wait below.
     int* kd_pre = nullptr;
+    bool k_late = false;
     if (x1_front && all_a) {
       if (!kh) {
         kh = w.kk_h.get(Q);
         pool_memcpy(kh, a->k, Q * sizeof(int));
       }
       kd_pre = w.kdev.get(Q);
-      CK(dmlp::dma_copy(kd_pre, kh, Q * sizeof(int), w.side));
+      k_late = kmin == kmax && !dr;
+      if (!k_late) CK(dmlp::dma_copy(kd_pre, kh, Q * sizeof(int), w.side));
     }
     // ---- device render: the rows (lossless int32, fp64 where a block is not 6-decimal) cross
     // PCIe on the side stream, the query block first, then the dataset, each block followed by its
@@ -456,7 +472,7 @@ struct Step {
           const int* s32;
           const double* s64;
           ship(a->Qx, a->Qr, 0, Q, at, Qd, &s32, &s64);
-          CKL(dmlp_render_rows(KT, A, s32, s64, 0, Q, Q, mud, Qd, 1, w.dq_hi.p, w.dq_n.p, nullptr,
+          CKL(dmlp_render_rows(KT, A, s32, s64, 0, Q, Q, mud, Qd, 1, qo_.hi_d, qo_.n_d, nullptr,
                                nullptr, rbad, drw + 8, nullptr, w.side));
           CK(mark(M_OPS, w.side));
           if (S_all > 0) CK(hipEventRecord(w.ev_ops, w.side));  // (the pipeline's screens: + chunk)
@@ -520,12 +536,14 @@ struct Step {
       uint16_t* xhi_h = w.sx_hi.get(nt * 64 * W);
       float* xin_h = w.sx_in.get(nt * 64);
       unsigned* xnm_h = w.sx_nm.get(2 + kEarlySlices);
-      uint16_t* qhi_h = w.sq_hi.get(Q * W);
-      float* qn_h = w.sq_n.get(Q);
       short* xhi = w.dx_hi.get(nt * 64 * W);
       float* xin = w.dx_in.get(nt * 64);
-      short* qhi = w.dq_hi.get(Q * W);
-      float* qn = w.dq_n.get(Q);
+      // the query operands: fragments, then norms, in one allocation each (query_ops)
+      qo_ = query_ops(w, Q, KT);
+      uint16_t* qhi_h = qo_.hi_h;
+      float* qn_h = qo_.n_h;
+      short* qhi = qo_.hi_d;
+      float* qn = qo_.n_d;
       if (!mu) mu = w.s_mu.get(A);
       if (pl && pl->rank != 0) {
         if (dmlp_plane_get_mu(pl, A, mu) != 0) throw Fail{-9};  // rank 0's centre, same bits
@@ -538,13 +556,10 @@ struct Step {
       auto h2d_tiles = [&](int64_t t0, int64_t t1, const double* qx, const double* const* qr,
                            int64_t nq, unsigned* xnm_hw, void* xhi_d, void* xin_d, void* xnm_d,
                            void* qhi_d, void* qn_d, int chunks) {
-        return a->Xr || a->Qr
-                   ? dmlp_host_ops_h2d_tiles_rows(a->Xr, N, t0, t1, qr, nq, A, mu, KT, xhi_h, xin_h,
-                                                  xnm_hw, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d,
-                                                  qn_d, chunks, w.side)
-                   : dmlp_host_ops_h2d_tiles(a->X, N, t0, t1, qx, nq, A, mu, KT, xhi_h, xin_h,
-                                             xnm_hw, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d,
-                                             chunks, w.side);
+        // (q_joined: qhi_d / qn_d are query_ops' pair, every call below passes all Q queries)
+        return dmlp_host_ops_h2d_tiles_q(a->X, a->Xr, N, t0, t1, qx, qr, nq, A, mu, KT, xhi_h,
+                                         xin_h, xnm_hw, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d,
+                                         qn_d, chunks, 1, w.side);
       };
       int rc;
       if (dr) {
@@ -599,6 +614,8 @@ struct Step {
         if (!dr) CK(mark(M_OPS, w.side));
         if (!dr || S_all == 0) CK(hipEventRecord(w.ev_ops, w.side));
         CK(hipStreamWaitEvent(st, w.ev_ops, 0));
+        // (uniform k: the array behind the operands' event, ahead of the rows' event)
+        if (k_late) CK(dmlp::dma_copy(kd_pre, kh, Q * sizeof(int), w.side));
         hx.xhi = xhi;
         hx.xin = xin;
         hx.words = words;
@@ -634,11 +651,12 @@ struct Step {
       L.rows = w.ev_rows;
       L.i32 = &i32_;
       if (with_hx && kd_pre) {
-        // (the words' zero copy and k's copy precede the operands' event on the side stream)
+        // (the words are zero and k's copy, or its scalar, precedes the operands' event)
         L.kd_pre = kd_pre;
         L.kk_pre = w.kk_h.p;
         L.all_a_pre = true;
         L.kmax_pre = kmax;
+        L.kuni_pre = k_late ? kmax : -1;
         L.ovf_pre = (int*)(words + kW_OVF);
       }
       if (rows_pending) {
@@ -708,8 +726,10 @@ struct Step {
         CK(mark(M_FORMAT, st));
         len_src = off + Q;
       }
+      static_assert(kW_N <= 64, "k_pack_small clears the words with one 64-thread block");
       hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(64), 0, st, len_src, Lp->ovf,
-                         a->early ? estats : nullptr, dr_bad, small_dev ? small_dev : small_d);
+                         a->early ? estats : nullptr, dr_bad, small_dev ? small_dev : small_d,
+                         words, (int)kW_N);
       CK(hipGetLastError());
       if (!small_dev) CK(dmlp::dma_copy(small, small_d, 8 * sizeof(int64_t), st));
       if (want_report && a->report_mode == 1 && !direct)
@@ -766,6 +786,8 @@ struct Step {
     g_stats.early = a->early;
     g_stats.device_render = dr && use_hx ? 1 : 0;
     g_stats.report_direct = direct ? 1 : 0;
+    // every render() above ended with the words cleared and the stream drained behind it
+    w.words_clean = words;
     return 0;
   }
 
@@ -828,11 +850,11 @@ struct Step {
     const int KT = dmlp_screen_kt(a->A);
     const int rc =
         a->Xr ? dmlp_host_ops_h2d_tiles_rows(a->Xr, a->N, t0, t1, nullptr, 0, a->A, mu, KT,
-                                             w.sx_hi.p, w.sx_in.p, xnm_h, w.sq_hi.p, w.sq_n.p, xhi,
-                                             xin, nullptr, w.dq_hi.p, w.dq_n.p, 1, w.side)
+                                             w.sx_hi.p, w.sx_in.p, xnm_h, qo_.hi_h, qo_.n_h, xhi,
+                                             xin, nullptr, qo_.hi_d, qo_.n_d, 1, w.side)
               : dmlp_host_ops_h2d_tiles(a->X, a->N, t0, t1, nullptr, 0, a->A, mu, KT, w.sx_hi.p,
-                                        w.sx_in.p, xnm_h, w.sq_hi.p, w.sq_n.p, xhi, xin, nullptr,
-                                        w.dq_hi.p, w.dq_n.p, 1, w.side);
+                                        w.sx_in.p, xnm_h, qo_.hi_h, qo_.n_h, xhi, xin, nullptr,
+                                        qo_.hi_d, qo_.n_d, 1, w.side);
     if (!(rc & 4)) {
       float nm;
       std::memcpy(&nm, xnm_h, 4);
@@ -842,6 +864,7 @@ struct Step {
     return rc;
   }
   const HostOps* hx_ = nullptr;  // (run(): the host operands of the early start)
+  QOps qo_{};                    // (run(): this call's query operands, query_ops)
 };
 }  // namespace dmlp_pipe
 

@@ -145,7 +145,8 @@ inline bool rowmajor_on() {
   static const bool on = !(getenv("DMLP_PAIR_ROWMAJOR") && getenv("DMLP_PAIR_ROWMAJOR")[0] == '0');
   return on;
 }
-// query render slices under the early start (profiles/r6i: 4 is best)
+// query render slices under the early start (profiles/r6i: 4 is best; still so with one copy per
+// slice: operands land at 0.235 / 0.260 / 0.263 ms with 4 / 6 / 8, profiles/r15a_front_and_check.txt)
 inline int early_qchunks() {
   static const int q = std::min(16, std::max(1, env_int("DMLP_FAST_QCHUNKS", 4)));
   return q;
@@ -390,8 +391,13 @@ struct Ctx {
       lf2_h, f64_h, f64_st_h;
   int64_t ident_len = 0;
   // dmlp_step: host-rendered operands (staging + device), rows, labels, outputs, report
-  HBuf<uint16_t> sx_hi, sq_hi;
-  HBuf<float> sx_in, sq_n;
+  HBuf<uint16_t> sx_hi;
+  HBuf<float> sx_in;
+  // the query operands, ONE allocation in staging and one on the device: the Q fragments
+  // (Q KT 64 bytes), then the Q norms directly behind them, so the last fragment chunk's copy
+  // carries the norms (prep.hip host_ops_h2d_tiles q_joined); a call's pointers: query_ops()
+  HBuf<char> sq_ops;
+  DBuf<char> dq_ops;
   HBuf<unsigned> sx_nm;
   HBuf<double> s_mu, s_f64;
   HBuf<int> s_i32, s_lab;
@@ -400,13 +406,19 @@ struct Ctx {
   hipEvent_t ev_done = nullptr;
   hipEvent_t ev_chunk[kEarlySlices] = {};  // the large-N pipeline's chunk events (rendered)
   hipEvent_t ev_copy[kEarlySlices] = {};   // ... and its chunks' rows landed
-  DBuf<short> dx_hi, dq_hi;
+  DBuf<short> dx_hi;
   DBuf<short> dx_row;  // the fp16 image point-major (dmlp_x1_rowmajor) for the pair refine
   DBuf<double> d_mu;   // device render: the centre
   DBuf<unsigned> dr_words;  // device render: [0, 8) slice done counters, [8, 72) query-block
                             // done counters, [72] out-of-range flag
-  DBuf<float> dx_in, dq_n;
-  DBuf<unsigned> dwords;  // the step's words (kW_*): cleared by one DMA copy per call
+  DBuf<float> dx_in;
+  // the step's words (kW_*): cleared for the next call by this call's tail (k_pack_small), or
+  // by one DMA copy in front of the operands when words_clean does not vouch for them
+  DBuf<unsigned> dwords;
+  // == dwords.p while the last dmlp_step on this workspace ran through its tail and nothing has
+  // written the words since; null on a fresh workspace, during a call, and after one that
+  // returned early or failed (a reallocated buffer no longer compares equal)
+  const unsigned* words_clean = nullptr;
   DBuf<int> d_i32, d_lab, d_lb;
   DBuf<double> d_X, d_Q, d_od;
   DBuf<int> d_oi;
@@ -418,9 +430,24 @@ struct Ctx {
 
 // dmlp_step's device words (Ctx::dwords): [kW_XNMAX] the image's max norm, [kW_BAD] out of range,
 // [kW_RDY, + kEarlySlices) the early start's ready words (norm bits), [kW_EST, + 4) early-start
-// counters, [kW_OVF] the overflow counter.  All zeroed per call (one DMA copy).
+// counters, [kW_OVF] the overflow counter.  All zero when a call starts (Ctx::dwords).
 constexpr int kW_XNMAX = 0, kW_BAD = 1, kW_RDY = 2, kW_EST = kW_RDY + kEarlySlices,
               kW_OVF = kW_EST + 4, kW_N = kW_OVF + 1;
+
+// One call's query operands inside Ctx::sq_ops / dq_ops: fragments at 0, norms at Q KT 64 bytes
+// (a multiple of 64: both stay aligned for any Q).
+struct QOps {
+  uint16_t* hi_h;
+  float* n_h;
+  short* hi_d;
+  float* n_d;
+};
+inline QOps query_ops(Ctx& w, int64_t Q, int KT) {
+  const size_t fb = (size_t)Q * KT * 64, all = fb + (size_t)Q * sizeof(float);
+  char* h = w.sq_ops.get(all);
+  char* d = w.dq_ops.get(all);
+  return {(uint16_t*)h, (float*)(h + fb), (short*)d, (float*)(d + fb)};
+}
 
 inline Ctx& ctx() {
   static Ctx c[16];

@@ -345,13 +345,22 @@ extern "C" int dmlp_host_unregister(void* p) {
 // completes).  *xnm_d gets this range's max norm; if the range holds data outside the screen's
 // range (return bit 1) it gets +inf instead, so a max-reduce over ranks tells every rank.
 // (rows: X / Qx row-major, or — Xr / Qr non-null — tables of row pointers)
+// q_joined: the caller states that the query norms lie directly behind the fragments in ONE
+// allocation, in staging and on the device alike (dmlp.h dmlp_host_ops_h2d_tiles_q): every query
+// chunk is then one copy and the last runs on through all the norms.  Each copy submission costs
+// the side stream 7.5-10 us whatever its size (profiles/r12m_query_slices_ab.txt), and no kernel
+// reads a norm before the last fragment chunk's event.
 static int host_ops_h2d_tiles(const double* X, const double* const* Xr, int64_t N, int64_t t0,
                               int64_t t1, const double* Qx, const double* const* Qr, int64_t Q,
                               int A, const double* mu, int KT, uint16_t* xhi_h, float* xin_h,
                               unsigned* xnm_h, uint16_t* qhi_h, float* qn_h, void* xhi_d,
                               void* xin_d, void* xnm_d, void* qhi_d, void* qn_d, int chunks,
-                              void* stream) {
+                              bool q_joined, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (q_joined && Q > 0 &&
+      ((const char*)qn_h != (const char*)(qhi_h + Q * KT * 32) ||
+       (const char*)qn_d != (const char*)qhi_d + Q * KT * 64))
+    return 4;  // (the stated layout does not hold: nothing rendered, nothing copied)
   const int64_t n_tiles = (N + 63) / 64;
   t0 = t0 < 0 ? 0 : (t0 > n_tiles ? n_tiles : t0);
   t1 = t1 < t0 ? t0 : (t1 > n_tiles ? n_tiles : t1);
@@ -394,8 +403,12 @@ static int host_ops_h2d_tiles(const double* X, const double* const* Xr, int64_t 
            : dmlp_cpu_prep_queries(Qx + q0 * A, q1 - q0, A, mu, KT, qhi_h + q0 * W, qn_h + q0))
       rc |= 2;
     mark();
-    h2d((char*)qhi_d + q0 * W * 2, qhi_h + q0 * W, (q1 - q0) * W * 2);
-    h2d((float*)qn_d + q0, qn_h + q0, (q1 - q0) * 4);
+    if (q_joined) {  // (the last chunk is never empty: q1 == Q > q0)
+      h2d((char*)qhi_d + q0 * W * 2, qhi_h + q0 * W, (q1 - q0) * W * 2 + (q1 == Q ? Q * 4 : 0));
+    } else {
+      h2d((char*)qhi_d + q0 * W * 2, qhi_h + q0 * W, (q1 - q0) * W * 2);
+      h2d((float*)qn_d + q0, qn_h + q0, (q1 - q0) * 4);
+    }
   }
   mark();
   if (dbg) {
@@ -414,7 +427,7 @@ extern "C" int dmlp_host_ops_h2d_tiles(const double* X, int64_t N, int64_t t0, i
                                        void* xnm_d, void* qhi_d, void* qn_d, int chunks,
                                        void* stream) {
   return host_ops_h2d_tiles(X, nullptr, N, t0, t1, Qx, nullptr, Q, A, mu, KT, xhi_h, xin_h, xnm_h,
-                            qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d, chunks, stream);
+                            qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d, chunks, false, stream);
 }
 extern "C" int dmlp_host_ops_h2d_tiles_rows(const double* const* Xr, int64_t N, int64_t t0,
                                             int64_t t1, const double* const* Qr, int64_t Q, int A,
@@ -423,7 +436,21 @@ extern "C" int dmlp_host_ops_h2d_tiles_rows(const double* const* Xr, int64_t N, 
                                             float* qn_h, void* xhi_d, void* xin_d, void* xnm_d,
                                             void* qhi_d, void* qn_d, int chunks, void* stream) {
   return host_ops_h2d_tiles(nullptr, Xr, N, t0, t1, nullptr, Qr, Q, A, mu, KT, xhi_h, xin_h,
-                            xnm_h, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d, chunks, stream);
+                            xnm_h, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d, chunks, false,
+                            stream);
+}
+extern "C" int dmlp_host_ops_h2d_tiles_q(const double* X, const double* const* Xr, int64_t N,
+                                         int64_t t0, int64_t t1, const double* Qx,
+                                         const double* const* Qr, int64_t Q, int A,
+                                         const double* mu, int KT, uint16_t* xhi_h, float* xin_h,
+                                         unsigned* xnm_h, uint16_t* qhi_h, float* qn_h,
+                                         void* xhi_d, void* xin_d, void* xnm_d, void* qhi_d,
+                                         void* qn_d, int chunks, int q_joined, void* stream) {
+  const bool rows = Xr || Qr;
+  return host_ops_h2d_tiles(rows ? nullptr : X, rows ? Xr : nullptr, N, t0, t1,
+                            rows ? nullptr : Qx, rows ? Qr : nullptr, Q, A, mu, KT, xhi_h, xin_h,
+                            xnm_h, qhi_h, qn_h, xhi_d, xin_d, xnm_d, qhi_d, qn_d, chunks,
+                            q_joined != 0, stream);
 }
 
 // The whole image (tiles [0, n_tiles)).

@@ -52,8 +52,10 @@ struct X1Cfg {
   // sub-buffer counts during a compaction); CP = 4 (mod 8) puts the 64 lanes of an append (16
   // columns x 4 sub-buffers, same fill) on 64 distinct banks
   static constexpr int CP = 4 * SUB + 4;
-  // the fill check runs every CHECK steps, so a sub-buffer is compacted once it holds more than
-  // SUB - CHECK entries (CHECK more appends always fit) and keeps at most SUB - CHECK of them
+  // CHECK is the sub-buffer's reserve in slots: a sub-buffer is compacted once a fill check
+  // finds more than SUB - CHECK entries in it and keeps at most SUB - CHECK of them, so at most
+  // CHECK appends may fall between two checks.  Per step that is a check every CHECK steps; the
+  // pair epilogue appends once per two steps and checks every 2 CHECK (k_screen_x1 PERIOD)
   static constexpr int CAPE = 4 * (SUB - CHECK);  // group entries a column may keep
   // group-id stride per (query, slice): the k class's (x1_sub: 16 or 32)
   static constexpr int IDCAP = 4 * ((SUB <= 16 ? 16 : 32) - 1);
@@ -91,12 +93,14 @@ template <int KT, int SUB, int DEPTH, int CHECK, bool COLLECT, bool F16>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 || KT >= 4) ? 1 : 2))) void k_screen_x1(
     const u32x4* __restrict__ xfrag, const f32x4* __restrict__ xinit4, int n_tiles, int n_points,
     const bf16x8* __restrict__ qhi, const float* __restrict__ qn, const int* __restrict__ qidx,
-    const int* __restrict__ qk, int nq, const unsigned* __restrict__ xnmax_bits,
+    const int* __restrict__ qk, int kuni, int nq, const unsigned* __restrict__ xnmax_bits,
     const unsigned* __restrict__ bad, float r1, float r2, float r3, int S, int s_first, int S_l,
     int tiles_per_slice, int n_qblocks, int hl, int* __restrict__ cand_ids,
     int* __restrict__ cand_cnt, float* __restrict__ cand_h, const float* __restrict__ hseed,
     int ccap, const unsigned* __restrict__ rdy, int rdy_tiles, int rdy_n,
     unsigned* __restrict__ estats, long long rdy_to) {
+  // kuni >= 0: every query's k is kuni and qk is not read (the native step with uniform k: its k
+  // array then crosses PCIe behind the screen's launch, not in front of it); < 0: k = qk[q]
   // COLLECT (large k, second pass): the threshold is fixed at the query's seed hseed[p] (a
   // lower bound on its k-th best score - 2 eps from the first pass); a full buffer is flushed to
   // the column's global list (up to ccap group entries per (query, slice)) instead of compacted
@@ -107,7 +111,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
   // step's append VALU halve (the screen is VALU-issue-bound: ~8.6 VALU per MFMA).  The
   // refine expands each entry to its 8 members (dmlp_screen_x1_group_rows).
   constexpr bool PAIR = x1_pair(COLLECT, KT, SUB);
-  static_assert(!PAIR || (CHECK == 2 && DEPTH == 4), "the pair epilogue assumes 2-step checks");
+  // steps between two fill checks.  PAIR: one per ring iteration (at r = 3) — its two appends (at
+  // r = 0 and r = 2) take a sub-buffer from at most SUB - CHECK = SUB - 2 entries to at most SUB,
+  // the second one's branch-free miss write lands in slot SUB - 1 at the most, and the compaction
+  // reads counts up to SUB as it always did.  The kept set does not depend on the cadence: a
+  // column's final threshold is the k-th largest key of all it has seen minus 2 eps, and every
+  // group at or above it was appended whatever the threshold was then; only a list's order may
+  // differ.  (Checking at r = 1 as well cost 4 v_cmp, 3 s_or, an s_cmp and a branch per pair: the
+  // VALU -> SGPR -> SALU -> branch tail this loop is bound by, profiles/r15a_front_and_check.txt.)
+  constexpr int PERIOD = PAIR ? 2 * CHECK : CHECK;
+  static_assert(!PAIR || (CHECK == 2 && DEPTH == 4 && PERIOD == DEPTH),
+                "the pair epilogue: a reserve of 2 slots, 2 appends and 1 check per ring iteration");
   constexpr int CT = C::CT;
   constexpr int D = C::D;
   constexpr int NH = C::NCOL / 64;  // columns per lane in the lane-owns-column phases
@@ -250,7 +264,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
     const float sd = COLLECT && valid ? hseed[p] : -FLT_MAX;
     const bool sbad = COLLECT && sd == INFINITY;
     oh[hb] = valid && !sbad ? (COLLECT ? fmaxf(sd, -FLT_MAX) : -FLT_MAX) : INFINITY;
-    okk[hb] = valid ? qk[q] : 0;
+    okk[hb] = valid ? (kuni >= 0 ? kuni : qk[q]) : 0;
     oe[hb] = valid ? eps_of(qn[q], xnmax) : 0.0f;
     ofl[hb] = sbad ? 1 : 0;
   }
@@ -466,10 +480,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
   // unconditional epilogue VALU of the step before it; left alone, the scheduler issues the MFMAs
   // back to back and the VALU behind them, where the wave can use none of its own MFMA issue
   // stalls (a 16x16x32 MFMA holds the vector issue for 8 of its 16 cycles).  The group barriers
-  // put NV of them behind each column tile's MFMAs.  The work of a pair is split evenly: the first
-  // step's four 4-row maxima (pinned to that slot by the empty asm) and the fill compares go
-  // under the second step's MFMAs, the second step's v_max3 and the hit compares under the next
-  // pair's first step.  NV = 6 packs a slot's 13-14 VALU behind its first two MFMAs, so every
+  // put NV of them behind each column tile's MFMAs.  The work of a pair is split: the first
+  // step's four 4-row maxima (pinned to that slot by the empty asm) go under the second step's
+  // MFMAs — with the iteration's fill compares in its last slot (r = 3) —, the second step's v_max3
+  // and the hit compares under the next pair's first step.  NV = 6 packs a slot's 13-14 VALU behind its first two MFMAs, so every
   // compare has issued before the last two: their SGPR results, the s_or chain and the branch
   // resolve under those MFMAs instead of behind them (an even spread, NV = 3, measured no
   // better than no interleave at all: profiles/r14a_screen_interleave.txt).  The order of every
@@ -522,16 +536,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
       }                                                                                         \
     }                                                                                           \
   } while (0)
-  // one compaction call site per CHECK steps (each inlined copy is ~8 KiB of code: one per
+  // one compaction call site per PERIOD steps (each inlined copy is ~8 KiB of code: one per
   // step of the unrolled ring would not stay in the instruction cache)
 #define DMLP_CHECK()                                                                            \
   do {                                                                                          \
     /* the fill test at the check point itself (addresses only grow between checks): one    \
-       compare per column tile every CHECK steps instead of one per tile per taken step */   \
+       compare per column tile every PERIOD steps instead of one per tile per taken step */  \
     unsigned long long trig = 0;                                                                \
     _Pragma("unroll") for (int ct = 0; ct < CT; ++ct)                                           \
       trig |= __builtin_amdgcn_ballot_w64(addr[ct] > lim[ct]);                                  \
-    DMLP_INTERLEAVE(); /* (PAIR: the checks sit in the slots of the pairs' second steps) */     \
+    DMLP_INTERLEAVE(); /* (PAIR: the check sits in the slot of a pair's second step) */         \
     if (trig) compact(false);                                                                   \
   } while (0)
 
@@ -631,9 +645,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SUB == 32 |
         }
         DMLP_LOAD(j + D, r);
         DMLP_EPILOGUE((r + 1) & 1, j - 1, (r + 1) & 1);  // (j = 0: of -inf, see acc)
-        // (PAIR: the appends come at even r — the pairs end at odd steps — and CHECK = 2 puts a
-        // check one step behind each)
-        if (r % CHECK == CHECK - 1) DMLP_CHECK();
+        // (PAIR: the appends come at even r — the pairs end at odd steps — and the one check of
+        // the iteration one step behind the second; the r = 1 slot keeps its packing, with the
+        // pair's first maxima alone behind its first MFMAs)
+        if (r % PERIOD == PERIOD - 1) DMLP_CHECK();
+        else if (PAIR && (r & 1)) DMLP_INTERLEAVE();
       }
     }
     // the last issued step (padded up to a multiple of D)
@@ -682,7 +698,7 @@ int x1_sub(int KT, int kmax) {
 // per-tile / exec-masked appends, the query-block early start: profiles/README.md, r9*.)
 template <int KT, int SUB, int DEPTH, int CHECK, bool F16>
 int launch_x1(int hl, const void* xfrag, const float* xinit, int64_t n_tiles, int64_t n_points,
-              const void* qhi, const float* qn, const int* qidx, const int* qk, int nq,
+              const void* qhi, const float* qn, const int* qidx, const int* qk, int kuni, int nq,
               const unsigned* xnmax, const unsigned* bad, float r1, float r2, float r3, int S,
               int s_first, int S_l, int* cand_ids, int* cand_cnt, float* cand_h,
               hipStream_t stream, const float* hseed = nullptr, int ccap = 0,
@@ -696,8 +712,8 @@ int launch_x1(int hl, const void* xfrag, const float* xinit, int64_t n_tiles, in
 #define DMLP_X1_LAUNCH(COLL)                                                                    \
   hipLaunchKernelGGL((k_screen_x1<KT, SUB, DEPTH, CHECK, COLL, F16>), dim3((unsigned)grid),     \
                      dim3(64), C::LDS, stream, (const u32x4*)xfrag, (const f32x4*)xinit,        \
-                     (int)n_tiles, (int)n_points, (const bf16x8*)qhi, qn, qidx, qk, nq, xnmax,  \
-                     bad, r1, r2, r3, S, s_first, S_l, tps, n_qblocks, hl, cand_ids, cand_cnt,  \
+                     (int)n_tiles, (int)n_points, (const bf16x8*)qhi, qn, qidx, qk, kuni, nq,   \
+                     xnmax, bad, r1, r2, r3, S, s_first, S_l, tps, n_qblocks, hl, cand_ids, cand_cnt, \
                      cand_h, hseed, ccap, rdy, rdy_tiles, rdy_n, estats, rdy_to)
   if (hseed) {  // the COLLECT pass (SUB = 16, fp16 only: see dmlp_screen_x1_collect)
     if constexpr (SUB == 16 && F16) DMLP_X1_LAUNCH(true);
@@ -823,7 +839,7 @@ extern "C" int dmlp_screen_x1_collect(int KT, int A, const void* xfrag, const fl
   hipStream_t st = (hipStream_t)stream;
 #define DMLP_X1C(KTV)                                                                           \
   return launch_x1<KTV, 16, 4, 2, true>(1, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx, qk,  \
-                                       nq, xnmax_bits, bad, r1, r2, r3, S, 0, S, cand_ids,      \
+                                       -1, nq, xnmax_bits, bad, r1, r2, r3, S, 0, S, cand_ids,      \
                                        cand_cnt, cand_h, st, hseed, ccap)
   if (KT == 1) DMLP_X1C(1);
   if (KT == 2) DMLP_X1C(2);
@@ -834,13 +850,15 @@ extern "C" int dmlp_screen_x1_collect(int KT, int A, const void* xfrag, const fl
 
 // Slices [s_first, s_first + S_l) of an S-slice screen (cand_* laid out for all S slices): a
 // caller streaming the dataset in chunks screens each chunk's slices as soon as it landed.
-extern "C" int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, const float* xinit,
-                                   int64_t n_tiles, int64_t n_points, const void* qhi,
-                                   const float* qn, const int* qidx, const int* qk, int nq,
-                                   int kmax, const unsigned* xnmax_bits, const unsigned* bad,
-                                   int S, int s_first, int S_l, int* cand_ids, int* cand_cnt,
-                                   float* cand_h, void* stream) {
+// kuni >= 0: every query's k (qk is not read, may be null); < 0: qk[q].
+extern "C" int dmlp_screen_x1_part_k(int KT, int hl, int A, const void* xfrag, const float* xinit,
+                                     int64_t n_tiles, int64_t n_points, const void* qhi,
+                                     const float* qn, const int* qidx, const int* qk, int kuni,
+                                     int nq, int kmax, const unsigned* xnmax_bits,
+                                     const unsigned* bad, int S, int s_first, int S_l,
+                                     int* cand_ids, int* cand_cnt, float* cand_h, void* stream) {
   if (nq <= 0 || S_l <= 0) return 0;
+  if (kuni > kmax) return -1;
   if (S < 1 || s_first < 0 || s_first + S_l > S || n_tiles < 0 || n_tiles > 0x7fffffff / 64 ||
       n_points > n_tiles * 64)
     return -1;
@@ -850,7 +868,7 @@ extern "C" int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, con
   float r1, r2, r3;
   dmlp_screen_x1_bound2(A, hl, &r1, &r2, &r3);
   hipStream_t st = (hipStream_t)stream;
-#define DMLP_X1_ARGS hl, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx, qk, nq, xnmax_bits, bad, r1, \
+#define DMLP_X1_ARGS hl, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx, qk, kuni, nq, xnmax_bits, bad, r1, \
                      r2, r3, S, s_first, S_l, cand_ids, cand_cnt, cand_h, st
   const bool s32 = x1_sub(KT, kmax) == 32;
   // hl = 1: the host's fp16 image + fp16 query fragments; hl = 2: prep.hip's bf16 hi/lo image
@@ -871,6 +889,17 @@ extern "C" int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, con
 #undef DMLP_X1_ARGS
 }
 
+extern "C" int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, const float* xinit,
+                                   int64_t n_tiles, int64_t n_points, const void* qhi,
+                                   const float* qn, const int* qidx, const int* qk, int nq,
+                                   int kmax, const unsigned* xnmax_bits, const unsigned* bad,
+                                   int S, int s_first, int S_l, int* cand_ids, int* cand_cnt,
+                                   float* cand_h, void* stream) {
+  return dmlp_screen_x1_part_k(KT, hl, A, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx, qk, -1,
+                               nq, kmax, xnmax_bits, bad, S, s_first, S_l, cand_ids, cand_cnt,
+                               cand_h, stream);
+}
+
 extern "C" int dmlp_screen_x1(int KT, int hl, int A, const void* xfrag, const float* xinit,
                               int64_t n_tiles, int64_t n_points, const void* qhi, const float* qn,
                               const int* qidx, const int* qk, int nq, int kmax,
@@ -884,13 +913,15 @@ extern "C" int dmlp_screen_x1(int KT, int hl, int A, const void* xfrag, const fl
 // (pipeline.hip's early start): one data slice per workgroup (S = 1), rdy[i] != 0 once image
 // tiles [i rdy_tiles, (i + 1) rdy_tiles) landed, its value the slice's max norm (fp32 bits).  The
 // result is the one dmlp_screen_x1(KT, 1, ...) gives with S = 1 once every slice landed.
-extern "C" int dmlp_screen_x1_early(int KT, int A, const void* xfrag, const float* xinit,
-                                    int64_t n_tiles, int64_t n_points, const void* qhi,
-                                    const float* qn, const int* qidx, const int* qk, int nq,
-                                    int kmax, const unsigned* bad, const unsigned* rdy,
-                                    int rdy_tiles, int rdy_n, int* cand_ids, int* cand_cnt,
-                                    float* cand_h, unsigned* estats, void* stream) {
+// (kuni: as dmlp_screen_x1_part_k)
+extern "C" int dmlp_screen_x1_early_k(int KT, int A, const void* xfrag, const float* xinit,
+                                      int64_t n_tiles, int64_t n_points, const void* qhi,
+                                      const float* qn, const int* qidx, const int* qk, int kuni,
+                                      int nq, int kmax, const unsigned* bad, const unsigned* rdy,
+                                      int rdy_tiles, int rdy_n, int* cand_ids, int* cand_cnt,
+                                      float* cand_h, unsigned* estats, void* stream) {
   if (nq <= 0) return 0;
+  if (kuni > kmax) return -1;
   if (n_tiles < 1 || n_tiles > 4096 || n_points > n_tiles * 64 || !rdy || rdy_tiles < 1 ||
       rdy_n < 1 || (int64_t)rdy_tiles * rdy_n < n_tiles)
     return -1;
@@ -911,7 +942,7 @@ extern "C" int dmlp_screen_x1_early(int KT, int A, const void* xfrag, const floa
   const bool s32 = x1_sub(KT, kmax) == 32;
 #define DMLP_X1E(KTV, SUBV)                                                                     \
   return launch_x1<KTV, SUBV, 4, 2, true>(1, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx,    \
-                                         qk, nq, bad, bad, r1, r2, r3, 1, 0, 1, cand_ids,       \
+                                         qk, kuni, nq, bad, bad, r1, r2, r3, 1, 0, 1, cand_ids,       \
                                          cand_cnt, cand_h, st, nullptr, 0, rdy, rdy_tiles,      \
                                          rdy_n, estats, rdy_to)
   if (KT == 1) { if (s32) DMLP_X1E(1, 32); DMLP_X1E(1, 16); }
@@ -920,4 +951,15 @@ extern "C" int dmlp_screen_x1_early(int KT, int A, const void* xfrag, const floa
   if (s32) DMLP_X1E(8, 32);
   DMLP_X1E(8, 16);
 #undef DMLP_X1E
+}
+
+extern "C" int dmlp_screen_x1_early(int KT, int A, const void* xfrag, const float* xinit,
+                                    int64_t n_tiles, int64_t n_points, const void* qhi,
+                                    const float* qn, const int* qidx, const int* qk, int nq,
+                                    int kmax, const unsigned* bad, const unsigned* rdy,
+                                    int rdy_tiles, int rdy_n, int* cand_ids, int* cand_cnt,
+                                    float* cand_h, unsigned* estats, void* stream) {
+  return dmlp_screen_x1_early_k(KT, A, xfrag, xinit, n_tiles, n_points, qhi, qn, qidx, qk, -1, nq,
+                                kmax, bad, rdy, rdy_tiles, rdy_n, cand_ids, cand_cnt, cand_h,
+                                estats, stream);
 }
