@@ -15,97 +15,57 @@
 Semantics are the reference's: exact fp64 squared-L2 distances summed left to
 right without FMA, neighbours ordered by (distance asc, id desc).  On a GPU the dataset is
 prepared once at fit() (fp64 copy + bf16x3 MFMA fragments) and reused by every query batch;
-on a CPU the native threaded brute force (or the KD-tree) runs.
+on a CPU the native threaded brute force (or the KD-tree) runs.  The fitted rows, update(), the
+search behind kneighbors() and the row selection of the leave-one-out calls are _knn_base.KNNBase's,
+shared with KNNRegressor; this class adds the votes over the lists the search leaves.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from ..ops import knn as K
+from ..ops.knn import _torch
+from ._knn_base import KNNBase
 
 
-def _torch():
-    import torch
-    return torch
-
-
-class KNNClassifier:
-    def __init__(self, device: str = "auto", exact: bool = False, cpu_method: str = "brute"):
-        torch = _torch()
-        self.on_gpu = device == "gpu" or (device == "auto" and torch.cuda.is_available())
-        self.exact = exact
-        self.cpu_method = cpu_method
-        self._ds = None
-
+class KNNClassifier(KNNBase):
     def fit(self, X, y):
-        self.X = np.ascontiguousarray(X, np.float64)
+        self._fit_rows(X)
         self.y = np.ascontiguousarray(y, np.int32)
-        if self.X.ndim != 2 or self.y.shape[0] != self.X.shape[0]:
+        if self.y.shape[0] != self.X.shape[0]:
             raise ValueError("X must be [N, A] and y [N]")
         lo = int(self.y.min()) if len(self.y) else 0
         hi = int(self.y.max()) + 1 if len(self.y) else 1
         self._label_range = (lo, hi)
         if self.on_gpu:
             torch = _torch()
-            self._ds = K.prepare_dataset(torch.from_numpy(self.X).cuda(),
-                                         torch.from_numpy(self.y).cuda(), (lo, hi))
+            self._yd = torch.from_numpy(self.y).cuda()
+            self._ds = self._prepare(torch.from_numpy(self.X).cuda())
         return self
 
-    def update(self, updates):
-        """Apply Update records (common.h:22-25) to the fitted dataset: rows are replaced in the
-        host copy and, on a GPU, scattered into the device copy, after which the screen layout
-        (centering, bf16 fragments, norms) is rebuilt so later queries stay exact."""
-        updates = list(updates)
-        if not updates:
-            return self
-        for u in updates:
-            if not 0 <= u.id < self.X.shape[0] or len(u.new_attrs) != self.X.shape[1]:
-                raise ValueError(f"update {u.id}: id out of range or wrong attribute count")
-            self.X[u.id] = np.asarray(u.new_attrs, np.float64)
-        if self.on_gpu:
-            torch = _torch()
-            ids = np.array(sorted({u.id for u in updates}), np.int64)
-            Xd = self._ds.X
-            Xd[torch.from_numpy(ids).to(Xd.device)] = torch.from_numpy(self.X[ids]).to(Xd.device)
-            self._ds = K.prepare_dataset(Xd, self._ds.labels, (self._ds.label_lo, self._ds.label_hi))
-        return self
+    def _prepare(self, Xd):
+        return K.prepare_dataset(Xd, self._yd, self._label_range)
 
-    def _k(self, Q, k):
-        if np.isscalar(k):
-            return np.full(Q.shape[0], int(k), np.int32)
-        return np.ascontiguousarray(k, np.int32)
-
-    def _run(self, Q, k, finalize):
+    def _run(self, Q, k):
+        """(labels, checksums) of the majority vote: on a GPU the vote and the checksum are fused
+        into the search (ONE knn_gpu call, nothing but the two results crosses back)."""
         Q = np.ascontiguousarray(Q, np.float64)
         kk = self._k(Q, k)
         if self.on_gpu:
-            torch = _torch()
-            r = K.knn_gpu(self._ds, torch.from_numpy(Q).cuda(), kk, finalize=finalize,
+            r = K.knn_gpu(self._ds, _torch().from_numpy(Q).cuda(), kk, finalize=True,
                           exact=self.exact)
-            d, i = r.dist.cpu().numpy(), r.ids.cpu().numpy()
-            lab = r.label.cpu().numpy() if r.label is not None else None
-            cs = r.checksum.cpu().numpy().view(np.uint64) if r.checksum is not None else None
-            return d, i, lab, cs, kk
-        d, i = K.knn_cpu(self.X, Q, kk, method=self.cpu_method)
-        lab = cs = None
-        if finalize:
-            lab, cs = K.finalize_cpu(i, kk, self.y)
-        return d, i, lab, cs, kk
-
-    def kneighbors(self, Q, k):
-        """(dist [Q, kmax], ids [Q, kmax]); row q is valid up to k_q, padded with (+inf, -1)."""
-        d, i, _, _, _ = self._run(Q, k, finalize=False)
-        return d, i
+            return r.label.cpu().numpy(), r.checksum.cpu().numpy().view(np.uint64)
+        return K.finalize_cpu(self._search(Q, kk)[1], kk, self.y)
 
     def predict(self, Q, k, weights: str = "uniform"):
         """The vote of the k nearest neighbours.  weights="inv_sqdist": the class with the largest
         (score, count, label) of predict_proba's weighted scores instead of the majority."""
         if weights == "uniform":
-            return self._run(Q, k, finalize=True)[2]
+            return self._run(Q, k)[0]
         return self._host(self._scores(Q, k, weights)[2])
 
     def checksums(self, Q, k):
-        return self._run(Q, k, finalize=True)[3]
+        return self._run(Q, k)[1]
 
     # ------------------------------------------------------------ class scores
     # Per-class votes are a function of the lists the search leaves on the device: one search
@@ -123,21 +83,14 @@ class KNNClassifier:
     def _scores(self, Q, k, weights):
         """(count [Q, C] int32, score [Q, C] float64, label [Q] int32) of the k nearest neighbours,
         on the device for a GPU (_host brings one back)."""
-        if weights not in K.VOTE_WEIGHTS:
-            raise ValueError(f"weights must be one of {sorted(K.VOTE_WEIGHTS)}, not {weights!r}")
+        K._weight_mode(weights, True)
         lo, nclass = int(self.classes_[0]), len(self.classes_)
         Q = np.ascontiguousarray(Q, np.float64)
         kk = self._k(Q, k)
+        d, i = self._search(Q, kk)
         if self.on_gpu:
-            torch = _torch()
-            r = K.knn_gpu(self._ds, torch.from_numpy(Q).cuda(), kk, finalize=False,
-                          exact=self.exact)
-            return K.vote_scores_gpu(r.ids, kk, self._ds.labels, lo, nclass, weights, dist=r.dist)
-        d, i = K.knn_cpu(self.X, Q, kk, method=self.cpu_method)
+            return K.vote_scores_gpu(i, kk, self._yd, lo, nclass, weights, dist=d)
         return K.vote_scores_cpu(i, kk, self.y, lo, nclass, weights, dist=d)
-
-    def _host(self, a):
-        return a.cpu().numpy() if self.on_gpu else a
 
     def predict_proba(self, Q, k, weights: str = "uniform"):
         """float64 [Q, len(classes_)]: the share of each class among the k nearest neighbours (k an
@@ -154,57 +107,26 @@ class KNNClassifier:
     # at kmax, then the vote-curve kernel (csrc/vote_curve.hip; dmlp_cpu_vote_curve on a CPU).
     def predict_curve(self, Q, kmax: int):
         """int32 [Q, kmax]: column k - 1 is predict(Q, k), bit for bit, from ONE search at kmax."""
-        kmax = int(kmax)
-        if not 1 <= kmax <= K.VOTE_CURVE_KMAX:
-            raise ValueError(f"kmax must be in [1, {K.VOTE_CURVE_KMAX}]")
+        kmax = self._curve_kmax(kmax)
         Q = np.ascontiguousarray(Q, np.float64)
         kk = np.full(Q.shape[0], kmax, np.int32)
+        _, i = self._search(Q, kk)
         if self.on_gpu:
-            torch = _torch()
-            r = K.knn_gpu(self._ds, torch.from_numpy(Q).cuda(), kk, finalize=False,
-                          exact=self.exact)
-            return K.vote_curve_gpu(r.ids, kk, self._ds.labels, kmax)[0].cpu().numpy()
-        _, i = K.knn_cpu(self.X, Q, kk, method=self.cpu_method)
+            return K.vote_curve_gpu(i, kk, self._yd, kmax)[0].cpu().numpy()
         return K.vote_curve_cpu(i, kk, self.y, kmax)[0]
 
-    def _loo_kmax(self, kmax):
-        kmax = int(kmax)
-        if not 1 <= kmax < K.VOTE_CURVE_KMAX:  # the search runs at kmax + 1: the row itself
-            raise ValueError(f"kmax must be in [1, {K.VOTE_CURVE_KMAX - 1}]")
-        return kmax
-
     def _loo_batch(self, rows, kmax, lists, hits=None):
-        """Dataset rows `rows` (a slice with step 1, or an int array) as queries at k = min(kmax +
-        1, N), then the curve with skip = the row's own id: (labels, hits, lists), on the device
-        for a GPU.  With duplicates the row need not lead its own list, and when more than kmax +
-        1 points tie at distance 0 it may be absent: the first kmax entries are then the answer,
-        which is what dropping the id wherever it sits (or nowhere) gives."""
-        N = self.X.shape[0]
-        ks = max(1, min(kmax + 1, N))
-        if isinstance(rows, slice):
-            idx = np.arange(*rows.indices(N), dtype=np.int32)
-        else:
-            idx = np.ascontiguousarray(rows, np.int64)
-            if idx.ndim != 1 or (len(idx) and (idx.min() < -N or idx.max() >= N)):
-                raise ValueError("rows must be a slice or a 1-d array of row ids")
-            idx = np.where(idx < 0, idx + N, idx).astype(np.int32)
-        kk = np.full(len(idx), ks, np.int32)
+        """The vote curve of the dataset rows `rows` over their nearest OTHER rows (_loo_lists, then
+        the curve with skip = the row's own id): (labels, hits, lists), on the device for a GPU —
+        the kept lists when `lists`, else the hits against the rows' own labels."""
+        d, i, kk, idx, skip = self._loo_lists(rows, kmax)
+        dist = d if lists else None
         if self.on_gpu:
-            torch = _torch()
-            ds = self._ds
-            if isinstance(rows, slice) and rows.indices(N)[2] == 1:
-                Qd = ds.X[idx[0]:idx[0] + len(idx)] if len(idx) else ds.X[:0]
-            else:  # a device-to-device gather: no host round trip
-                Qd = ds.X.index_select(0, torch.from_numpy(idx.astype(np.int64)).to(ds.X.device))
-            r = K.knn_gpu(ds, Qd, kk, finalize=False, exact=self.exact, kstride=ks)
-            me = torch.from_numpy(idx).to(ds.X.device)
-            return K.vote_curve_gpu(r.ids, kk, ds.labels, kmax, skip=me,
-                                    truth=ds.labels[me.long()] if not lists else None,
-                                    dist=r.dist if lists else None, hits=hits)
-        d, i = K.knn_cpu(self.X, self.X[idx], kk, kstride=ks, method=self.cpu_method)
-        return K.vote_curve_cpu(i, kk, self.y, kmax, skip=idx,
-                                truth=self.y[idx] if not lists else None,
-                                dist=d if lists else None, hits=hits)
+            truth = None if lists else self._yd[skip.long()]
+            return K.vote_curve_gpu(i, kk, self._yd, kmax, skip=skip, truth=truth, dist=dist,
+                                    hits=hits)
+        truth = None if lists else self.y[idx]
+        return K.vote_curve_cpu(i, kk, self.y, kmax, skip=skip, truth=truth, dist=dist, hits=hits)
 
     def loo_kneighbors(self, kmax: int, rows=None):
         """(dist, ids) [R, kmax]: the kmax nearest neighbours of the dataset rows `rows` (a slice
@@ -212,9 +134,7 @@ class KNNClassifier:
         when fewer than kmax other points exist.  kmax <= 255."""
         kmax = self._loo_kmax(kmax)
         _, _, (d, i) = self._loo_batch(slice(None) if rows is None else rows, kmax, lists=True)
-        if self.on_gpu:
-            return d.cpu().numpy(), i.cpu().numpy()
-        return d, i
+        return self._host(d), self._host(i)
 
     def loo_curve(self, kmax: int, batch_rows: int = 65536):
         """(hits int64 [kmax], N): hits[k - 1] = the rows whose k nearest OTHER rows vote their own
@@ -228,7 +148,7 @@ class KNNClassifier:
             _, hits, _ = self._loo_batch(slice(a, min(N, a + step)), kmax, lists=False, hits=hits)
         if hits is None:
             return np.zeros(kmax, np.int64), N
-        return (hits.cpu().numpy() if self.on_gpu else hits), N
+        return self._host(hits), N
 
     def select_k(self, kmax: int):
         """(best_k, accuracy float64 [kmax]): leave-one-out accuracy of every k <= kmax and the

@@ -20,7 +20,9 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            KNNRegressor's predict, predict_curve and leave-one-out curves
 CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu,
 vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu.  curve_sse (host, both devices)
-turns a mean curve into squared errors.
+turns a mean curve into squared errors.  The eight list-kernel wrappers check and normalise their
+lists in one place per backend (_host_lists, _device_lists), their weights in _weight_mode and
+their curve length in _check_kcap.
 
 Exactness contract (common.cpp:57-79, engine.cpp:12-18): distances are the
 reference's left-to-right fp64 sums without FMA; the MFMA screens only filter candidates, with a
@@ -91,6 +93,41 @@ def finalize_cpu(ids: np.ndarray, k: np.ndarray, labels: np.ndarray):
 
 
 VOTE_CURVE_KMAX = 256   # dmlp_vote_curve_kmax(): slots of a list the curve kernels read
+VOTE_WEIGHTS = {"uniform": 0, "inv_sqdist": 1}  # the mode of the score and mean kernels
+
+
+def _host_lists(ids, k, skip, dist, extra_q=()):
+    """The list arguments every host list kernel takes, as contiguous arrays: ids int32 [Q, kstride]
+    with kstride >= 1; k, skip and each of extra_q int32 [Q] (None stays None); dist float64 shaped
+    like ids.  Returns ((ids, k, skip, dist, *extra_q), (Q, kstride)), or ValueError."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 2 or ids.shape[1] < 1:
+        raise ValueError("ids must be [Q, kstride] with kstride >= 1")
+    Q = ids.shape[0]
+    k = np.ascontiguousarray(k, np.int32)
+    skip, *extra_q = (None if a is None else np.ascontiguousarray(a, np.int32)
+                      for a in (skip, *extra_q))
+    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
+    if any(a is not None and a.shape != (Q,) for a in (k, skip, *extra_q)) or \
+            (dist is not None and dist.shape != ids.shape):
+        raise ValueError("k, skip and truth must be [Q] and dist shaped like ids")
+    return (ids, k, skip, dist, *extra_q), ids.shape
+
+
+def _weight_mode(weights, have_dist: bool) -> int:
+    """The kernels' mode of a `weights` name, or ValueError."""
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"weights must be one of {sorted(VOTE_WEIGHTS)}, not {weights!r}")
+    if VOTE_WEIGHTS[weights] == 1 and not have_dist:
+        raise ValueError("weights='inv_sqdist' needs dist")
+    return VOTE_WEIGHTS[weights]
+
+
+def _check_kcap(kcap, name: str = "kcap") -> int:
+    kcap = int(kcap)
+    if not 1 <= kcap <= VOTE_CURVE_KMAX:
+        raise ValueError(f"{name} must be in [1, {VOTE_CURVE_KMAX}]")
+    return kcap
 
 
 def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
@@ -100,21 +137,9 @@ def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
     entries, repeated past the last one, -1 for an empty row —, hits int64 [kcap] | None — with
     truth [Q]: rows whose column j equals truth, ADDED to `hits` when one is passed —, (dist, ids)
     [Q, kcap] | None — with dist: the kept entries, padded with (+inf, -1))."""
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim != 2:
-        raise ValueError("ids must be [Q, kstride]")
-    Q, ks = ids.shape
-    k = np.ascontiguousarray(k, np.int32)
+    (ids, k, skip, dist, truth), (Q, ks) = _host_lists(ids, k, skip, dist, (truth,))
     labels = np.ascontiguousarray(labels, np.int32)
-    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
-    truth = None if truth is None else np.ascontiguousarray(truth, np.int32)
-    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
-    if len(k) != Q or any(a is not None and len(a) != Q for a in (skip, truth)) or \
-            (dist is not None and dist.shape != ids.shape):
-        raise ValueError("k, skip, truth must be [Q] and dist shaped like ids")
-    kcap = int(kcap)
-    if not 1 <= kcap <= VOTE_CURVE_KMAX:
-        raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
+    kcap = _check_kcap(kcap)
     lab = np.empty((Q, kcap), np.int32)
     od = np.empty((Q, kcap), np.float64) if dist is not None else None
     oi = np.empty((Q, kcap), np.int32) if dist is not None else None
@@ -133,22 +158,18 @@ def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
 
 
 VOTE_SCORES_CMAX = 4096  # dmlp_vote_scores_cmax(): classes a score launch takes
-VOTE_WEIGHTS = {"uniform": 0, "inv_sqdist": 1}  # the mode of dmlp_vote_scores
 
 
 def _score_mode(label_lo, nclass, weights, have_dist: bool):
     """(label_lo, nclass, mode) of a class-score call, or ValueError for what the C entry rejects."""
-    if weights not in VOTE_WEIGHTS:
-        raise ValueError(f"weights must be one of {sorted(VOTE_WEIGHTS)}, not {weights!r}")
+    mode = _weight_mode(weights, have_dist)
     nclass = int(nclass)
     if not 1 <= nclass <= VOTE_SCORES_CMAX:
         raise ValueError(f"nclass must be in [1, {VOTE_SCORES_CMAX}]")
-    if VOTE_WEIGHTS[weights] == 1 and not have_dist:
-        raise ValueError("weights='inv_sqdist' needs dist")
     label_lo = int(label_lo)
     if not -(1 << 31) <= label_lo < (1 << 31):
         raise ValueError("label_lo must be an int32")
-    return label_lo, nclass, VOTE_WEIGHTS[weights]
+    return label_lo, nclass, mode
 
 
 def vote_scores_cpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "uniform",
@@ -161,18 +182,9 @@ def vote_scores_cpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "
     list order, of 1 / d over its entries (d: dist, shaped like ids, the engine's SQUARED distances;
     a row with an entry at d == 0 counts those entries 1 and every other 0).  label is the class
     with the largest (score, count, label), -1 for a row that keeps nothing."""
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim != 2 or ids.shape[1] < 1:
-        raise ValueError("ids must be [Q, kstride] with kstride >= 1")
-    Q, ks = ids.shape
+    (ids, k, skip, dist), (Q, ks) = _host_lists(ids, k, skip, dist)
     label_lo, nclass, mode = _score_mode(label_lo, nclass, weights, dist is not None)
-    k = np.ascontiguousarray(k, np.int32)
     labels = np.ascontiguousarray(labels, np.int32)
-    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
-    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
-    if k.shape != (Q,) or (skip is not None and skip.shape != (Q,)) or \
-            (dist is not None and dist.shape != ids.shape):
-        raise ValueError("k and skip must be [Q] and dist shaped like ids")
     count = np.empty((Q, nclass), np.int32)
     score = np.empty((Q, nclass), np.float64)
     lab = np.empty(Q, np.int32)
@@ -216,34 +228,18 @@ NEIGHBOR_MEANS_TMAX = 256  # dmlp_neighbor_means_tmax(): target columns a mean l
 
 def _means_args(T, weights, have_dist: bool, kcap=None):
     """(T, mode, kcap) of a neighbour-mean call, or ValueError for what the C entry rejects."""
-    if weights not in VOTE_WEIGHTS:
-        raise ValueError(f"weights must be one of {sorted(VOTE_WEIGHTS)}, not {weights!r}")
+    mode = _weight_mode(weights, have_dist)
     if not 1 <= T <= NEIGHBOR_MEANS_TMAX:
         raise ValueError(f"targets must have between 1 and {NEIGHBOR_MEANS_TMAX} columns")
-    if VOTE_WEIGHTS[weights] == 1 and not have_dist:
-        raise ValueError("weights='inv_sqdist' needs dist")
-    if kcap is not None:
-        kcap = int(kcap)
-        if not 1 <= kcap <= VOTE_CURVE_KMAX:
-            raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
-    return int(T), VOTE_WEIGHTS[weights], kcap
+    return int(T), mode, None if kcap is None else _check_kcap(kcap)
 
 
 def _means_cpu_args(ids, k, targets, weights, dist, skip, kcap=None):
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim != 2 or ids.shape[1] < 1:
-        raise ValueError("ids must be [Q, kstride] with kstride >= 1")
-    Q = ids.shape[0]
+    (ids, k, skip, dist), _ = _host_lists(ids, k, skip, dist)
     targets = np.ascontiguousarray(targets, np.float64)
     if targets.ndim != 2:
         raise ValueError("targets must be [N, T]")
     T, mode, kcap = _means_args(targets.shape[1], weights, dist is not None, kcap)
-    k = np.ascontiguousarray(k, np.int32)
-    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
-    dist = None if dist is None else np.ascontiguousarray(dist, np.float64)
-    if k.shape != (Q,) or (skip is not None and skip.shape != (Q,)) or \
-            (dist is not None and dist.shape != ids.shape):
-        raise ValueError("k and skip must be [Q] and dist shaped like ids")
     return ids, k, targets, dist, skip, T, mode, kcap
 
 
@@ -740,6 +736,37 @@ def finalize_gpu(ds_labels, label_range, dist, ids, k_dev):
     return lab, cs
 
 
+def _like_ids(t, ids):
+    """t as a contiguous tensor of ids' dtype (int32) on ids' device; itself when it is one."""
+    return None if t is None else t.to(ids).contiguous()
+
+
+def _device_lists(ids, k, skip, dist, extra_q=()):
+    """_host_lists for torch tensors on one GPU: ids must be an int32 tensor already, its device is
+    the lists' device; k (a host array is copied over once), skip and each of extra_q end up int32
+    [Q] there; dist must be float64, shaped like ids, on that device.  No work is issued for
+    arguments that conform.  Returns ((ids, k, skip, dist, *extra_q), (Q, kstride)), or ValueError.
+    (Every wrapper call passes through here: plain loops, no generators.)"""
+    torch = _torch()
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
+        raise ValueError("ids must be an int32 [Q, kstride] tensor with kstride >= 1")
+    Q, ks = ids.shape
+    if not torch.is_tensor(k):
+        k = torch.from_numpy(np.ascontiguousarray(k, np.int32))
+    ids = ids.contiguous()
+    per_q = [k, skip, *extra_q]
+    for j, t in enumerate(per_q):
+        if t is not None:
+            per_q[j] = t = _like_ids(t, ids)
+            if t.shape != (Q,):
+                raise ValueError("k, skip and truth must be [Q]")
+    if dist is not None:
+        dist = dist.contiguous()
+        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != ids.device:
+            raise ValueError("dist must be a float64 tensor shaped like ids")
+    return (ids, per_q[0], per_q[1], dist, *per_q[2:]), (Q, ks)
+
+
 def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
     """vote_curve_cpu on the device (dmlp_vote_curve, csrc/vote_curve.hip): ids [Q, kstride] int32,
     k / skip / truth [Q] int32, labels [N] int32 and dist (shaped like ids, float64) are torch
@@ -747,25 +774,10 @@ def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
     counts are ADDED to (a fresh zeroed one when truth is given without it), so a caller can sum
     over batches of rows without a copy back.  Asynchronous on the current stream."""
     torch = _torch()
-    if ids.dim() != 2 or ids.dtype != torch.int32:
-        raise ValueError("ids must be an int32 [Q, kstride] tensor")
+    (ids, k, skip, dist, truth), (Q, ks) = _device_lists(ids, k, skip, dist, (truth,))
     dev = ids.device
-    Q, ks = ids.shape
-    if not torch.is_tensor(k):
-        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
-
-    def i32(t):
-        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
-    ids, k, labels, skip, truth = ids.contiguous(), i32(k), i32(labels), i32(skip), i32(truth)
-    if dist is not None:
-        dist = dist.contiguous()
-        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
-            raise ValueError("dist must be a float64 tensor shaped like ids")
-    if k.numel() != Q or any(a is not None and a.numel() != Q for a in (skip, truth)):
-        raise ValueError("k, skip, truth must be [Q]")
-    kcap = int(kcap)
-    if not 1 <= kcap <= VOTE_CURVE_KMAX:
-        raise ValueError(f"kcap must be in [1, {VOTE_CURVE_KMAX}]")
+    labels = _like_ids(labels, ids)
+    kcap = _check_kcap(kcap)
     lab = torch.empty((Q, kcap), dtype=torch.int32, device=dev)
     od = torch.empty((Q, kcap), dtype=torch.float64, device=dev) if dist is not None else None
     oi = torch.empty((Q, kcap), dtype=torch.int32, device=dev) if dist is not None else None
@@ -791,23 +803,10 @@ def vote_scores_gpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "
     nclass] float64, label [Q] int32) there, bit-identical to the CPU's.  Asynchronous on the
     current stream."""
     torch = _torch()
-    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
-        raise ValueError("ids must be an int32 [Q, kstride] tensor with kstride >= 1")
-    dev = ids.device
-    Q, ks = ids.shape
     label_lo, nclass, mode = _score_mode(label_lo, nclass, weights, dist is not None)
-    if not torch.is_tensor(k):
-        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
-
-    def i32(t):
-        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
-    ids, k, labels, skip = ids.contiguous(), i32(k), i32(labels), i32(skip)
-    if dist is not None:
-        dist = dist.contiguous()
-        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
-            raise ValueError("dist must be a float64 tensor shaped like ids")
-    if tuple(k.shape) != (Q,) or (skip is not None and tuple(skip.shape) != (Q,)):
-        raise ValueError("k and skip must be [Q]")
+    (ids, k, skip, dist), (Q, ks) = _device_lists(ids, k, skip, dist)
+    dev = ids.device
+    labels = _like_ids(labels, ids)
     # every slot is written: no fill pass
     count = torch.empty((Q, nclass), dtype=torch.int32, device=dev)
     score = torch.empty((Q, nclass), dtype=torch.float64, device=dev)
@@ -820,26 +819,11 @@ def vote_scores_gpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "
 
 def _means_gpu_args(ids, k, targets, weights, dist, skip, kcap=None):
     torch = _torch()
-    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
-        raise ValueError("ids must be an int32 [Q, kstride] tensor with kstride >= 1")
-    dev = ids.device
-    Q = ids.shape[0]
-    if targets.dim() != 2 or targets.dtype != torch.float64 or targets.device != dev:
+    (ids, k, skip, dist), _ = _device_lists(ids, k, skip, dist)
+    if targets.dim() != 2 or targets.dtype != torch.float64 or targets.device != ids.device:
         raise ValueError("targets must be a float64 [N, T] tensor on the lists' device")
     T, mode, kcap = _means_args(targets.shape[1], weights, dist is not None, kcap)
-    if not torch.is_tensor(k):
-        k = torch.from_numpy(np.ascontiguousarray(k, np.int32)).to(dev)
-
-    def i32(t):
-        return None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
-    ids, k, skip, targets = ids.contiguous(), i32(k), i32(skip), targets.contiguous()
-    if dist is not None:
-        dist = dist.contiguous()
-        if dist.shape != ids.shape or dist.dtype != torch.float64 or dist.device != dev:
-            raise ValueError("dist must be a float64 tensor shaped like ids")
-    if tuple(k.shape) != (Q,) or (skip is not None and tuple(skip.shape) != (Q,)):
-        raise ValueError("k and skip must be [Q]")
-    return ids, k, targets, dist, skip, T, mode, kcap
+    return ids, k, targets.contiguous(), dist, skip, T, mode, kcap
 
 
 def neighbor_means_gpu(ids, k, targets, weights: str = "uniform", dist=None, skip=None):
