@@ -121,6 +121,10 @@ _SIGS = {
     "dmlp_vote_curve_kmax": (i32, []),
     "dmlp_vote_curve": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "dmlp_cpu_vote_curve": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "dmlp_vote_curve_weighted": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                       vp, vp]),
+    "dmlp_cpu_vote_curve_weighted": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp,
+                                           vp, vp]),
     "dmlp_vote_scores_cmax": (i32, []),
     "dmlp_vote_scores": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dmlp_cpu_vote_scores": (i32, [vp, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp]),

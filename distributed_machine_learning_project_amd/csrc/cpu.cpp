@@ -274,6 +274,71 @@ extern "C" int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride,
   return 0;
 }
 
+extern "C" int dmlp_cpu_vote_curve_weighted(const double* d, const int* ids, int kstride,
+                                            const int* qk, int64_t Q, const int* skip,
+                                            const int* labels, int mode, int kcap, int* out_label,
+                                            double* out_score, double* out_d, int* out_i,
+                                            const int* truth, unsigned long long* hits) {
+  if (Q <= 0) return 0;
+  if (kcap < 1 || kcap > 256 || kstride < 1 || mode < 0 || mode > 1) return -1;
+  if ((out_d == nullptr) != (out_i == nullptr) || (truth == nullptr) != (hits == nullptr))
+    return -1;
+  if (!ids || !qk || !labels || !out_label || ((out_d || mode == 1) && !d)) return -1;
+  struct Run {
+    double s;
+    int c;
+  };
+  std::unordered_map<int, Run> run;
+  for (int64_t q = 0; q < Q; ++q) {
+    const int* iq = ids + q * kstride;
+    int* ol = out_label + q * kcap;
+    double* os = out_score ? out_score + q * kcap : nullptr;
+    const int n = std::min(std::min(qk[q], kstride), 256);
+    const int sk = skip ? skip[q] : -1;
+    run.clear();
+    // the running winner: the largest (score, count, label) key of the entries so far
+    int m = 0, best = -1, bc = 0;
+    double bs = 0.0;
+    bool zero = false;  // the first kept entry sits at distance 0: weights are 1 there, 0 elsewhere
+    for (int e = 0; e < n && m < kcap; ++e) {
+      const int id = iq[e];
+      if (id < 0 || id == sk) continue;
+      const int lb = labels[id];
+      Run& r = run.try_emplace(lb, Run{0.0, 0}).first->second;
+      ++r.c;
+      if (mode == 1) {
+        const double x = d[q * kstride + e];
+        if (m == 0) zero = x == 0.0;
+        r.s = r.s + (zero ? (x == 0.0 ? 1.0 : 0.0) : 1.0 / x);
+      } else {
+        r.s = (double)r.c;
+      }
+      if (m == 0 || r.s > bs || (r.s == bs && (r.c > bc || (r.c == bc && lb > best)))) {
+        bs = r.s;
+        bc = r.c;
+        best = lb;
+      }
+      if (out_i) {
+        out_i[q * kcap + m] = id;
+        out_d[q * kcap + m] = d[q * kstride + e];
+      }
+      if (os) os[m] = bs;
+      ol[m++] = best;
+    }
+    for (int j = m; j < kcap; ++j) {
+      ol[j] = m ? ol[m - 1] : -1;
+      if (os) os[j] = m ? os[m - 1] : 0.0;
+      if (out_i) {
+        out_i[q * kcap + j] = -1;
+        out_d[q * kcap + j] = INFINITY;
+      }
+    }
+    if (hits)
+      for (int j = 0; j < kcap; ++j) hits[j] += ol[j] == truth[q];
+  }
+  return 0;
+}
+
 extern "C" int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk,
                                     int64_t Q, const int* skip, const int* labels, int label_lo,
                                     int nclass, int mode, int* out_count, double* out_score,

@@ -523,6 +523,38 @@ int dmlp_vote_curve(const double* d, const int* ids, int kstride, const int* qk,
                     const int* skip, const int* labels, int kcap, int* out_label, double* out_d,
                     int* out_i, const int* truth, unsigned long long* hits, void* stream);
 
+// ---- device: weighted vote curve (prefix votes under per-entry weights)
+// dmlp_vote_curve with dmlp_vote_scores' weights.  Shared with dmlp_vote_curve: the slots read (the
+// first min(qk[q], kstride, 256)), which entries are kept, the compaction, out_d / out_i, truth /
+// hits (accumulating, integer atomics only) and the clamp m = min(#kept, kcap).  d is read in mode
+// 1, or when out_d is given; it may be null otherwise.
+//   weights: mode 0 (uniform) w_e = 1.  mode 1 (inverse SQUARED distance, VOTE_WEIGHTS' numbering):
+//     the row's FIRST kept entry decides, as d_ref does in the neighbour means, so that a weight
+//     does not depend on the length of a prefix: if its d == 0, w_e = 1.0 where d_e == 0 and 0.0
+//     elsewhere; otherwise w_e = 1.0 / d_e (IEEE division).  d = +inf weighs 0, a d whose inverse
+//     overflows weighs +inf — a later d == 0 of an unsorted list included.  On a list whose kept
+//     distances are non-decreasing, which is every list the search produces, this IS
+//     dmlp_vote_scores' rule: "some kept entry has d == 0" and "the first kept entry has d == 0"
+//     are the same statement there.  d holds no NaN and no negative value.
+//   keys: for kept entry e, s_e = the sum, in list order from 0.0 (fp64, __dadd_rn, no FMA), of the
+//     weights of the kept e' <= e with e's label (mode 0: (double)c_e), c_e their number, key_e =
+//     (s_e, c_e, label_e) compared in that order.  Weights are >= 0, so the largest key over a
+//     prefix is the largest (score, count, label) over its classes: dmlp_vote_scores' winner.
+//   out_label[q * kcap + j], j < m: the label of the largest key over the first j + 1 kept entries;
+//     j in [m, kcap) repeats slot m - 1, or holds -1 when m == 0.  Labels are any int.
+//   out_score (nullable) [nq][kcap]: that key's score — the winning class's score at the prefix —
+//     with the same repeat rule; 0.0 throughout when m == 0.
+// Mode 0 gives the bits dmlp_vote_curve gives.  Mode 1, on a list with non-decreasing kept
+// distances and labels inside [label_lo, label_lo + nclass): column j equals dmlp_vote_scores'
+// out_label, and the winner's out_score bits, on the first j + 1 kept entries.  The host twin gives
+// the same bits.  Every slot of the given outputs is written, nothing outside them.  nq <= 0
+// returns 0 and writes nothing; what dmlp_vote_curve refuses, mode outside {0, 1} or mode 1 with a
+// null d return -1 before any launch.
+int dmlp_vote_curve_weighted(const double* d, const int* ids, int kstride, const int* qk, int nq,
+                             const int* skip, const int* labels, int mode, int kcap,
+                             int* out_label, double* out_score, double* out_d, int* out_i,
+                             const int* truth, unsigned long long* hits, void* stream);
+
 // ---- device: class scores (per-class vote counts and weighted votes of a neighbour list)
 // Row q < nq: slots e in [0, min(qk[q], kstride)) of ids[q * kstride ...] are read — the whole
 // list, no 256-slot clamp — and the same slots of d when mode == 1 (d may be null in mode 0).  An
@@ -617,6 +649,11 @@ int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stri
 int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                         const int* skip, const int* labels, int kcap, int* out_label,
                         double* out_d, int* out_i, const int* truth, unsigned long long* hits);
+// dmlp_vote_curve_weighted's contract on the host: a serial walk per row, the same bits.
+int dmlp_cpu_vote_curve_weighted(const double* d, const int* ids, int kstride, const int* qk,
+                                 int64_t Q, const int* skip, const int* labels, int mode, int kcap,
+                                 int* out_label, double* out_score, double* out_d, int* out_i,
+                                 const int* truth, unsigned long long* hits);
 // dmlp_vote_scores' contract on the host: a serial walk per row, bit-identical scores.
 int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                          const int* skip, const int* labels, int label_lo, int nclass, int mode,

@@ -11,6 +11,8 @@
     dist, ids = clf.loo_kneighbors(kmax)     # neighbours of the dataset's own rows, self excluded
     hits, N = clf.loo_curve(kmax)            # leave-one-out hits of every k <= kmax
     best_k, acc = clf.select_k(kmax)         # the smallest k with the best leave-one-out accuracy
+    best_k, acc = clf.select_k(kmax, weights="inv_sqdist")  # ... of the weighted vote (also on
+                                             # predict_curve and loo_curve)
 
 Semantics are the reference's: exact fp64 squared-L2 distances summed left to
 right without FMA, neighbours ordered by (distance asc, id desc).  On a GPU the dataset is
@@ -104,29 +106,37 @@ class KNNClassifier(KNNBase):
 
     # ------------------------------------------------------------ choosing k
     # The lists are sorted, so the vote for every k <= kmax is a function of one list: one search
-    # at kmax, then the vote-curve kernel (csrc/vote_curve.hip; dmlp_cpu_vote_curve on a CPU).
-    def predict_curve(self, Q, kmax: int):
-        """int32 [Q, kmax]: column k - 1 is predict(Q, k), bit for bit, from ONE search at kmax."""
+    # at kmax, then the vote-curve kernel (csrc/vote_curve.hip; dmlp_cpu_vote_curve on a CPU).  A
+    # non-uniform `weights` takes the weighted curve of the same file, which reads the search's
+    # distances as well; no label range is taken, so predict_proba's limit does not apply.
+    def predict_curve(self, Q, kmax: int, weights: str = "uniform"):
+        """int32 [Q, kmax]: column k - 1 is predict(Q, k, weights), bit for bit, from ONE search at
+        kmax."""
+        K._weight_mode(weights, True)
         kmax = self._curve_kmax(kmax)
         Q = np.ascontiguousarray(Q, np.float64)
         kk = np.full(Q.shape[0], kmax, np.int32)
-        _, i = self._search(Q, kk)
+        d, i = self._search(Q, kk)
+        dist = None if weights == "uniform" else d
         if self.on_gpu:
-            return K.vote_curve_gpu(i, kk, self._yd, kmax)[0].cpu().numpy()
-        return K.vote_curve_cpu(i, kk, self.y, kmax)[0]
+            return K.vote_curve_gpu(i, kk, self._yd, kmax, dist=dist, weights=weights,
+                                    lists=False)[0].cpu().numpy()
+        return K.vote_curve_cpu(i, kk, self.y, kmax, dist=dist, weights=weights, lists=False)[0]
 
-    def _loo_batch(self, rows, kmax, lists, hits=None):
+    def _loo_batch(self, rows, kmax, lists, hits=None, weights="uniform"):
         """The vote curve of the dataset rows `rows` over their nearest OTHER rows (_loo_lists, then
         the curve with skip = the row's own id): (labels, hits, lists), on the device for a GPU —
-        the kept lists when `lists`, else the hits against the rows' own labels."""
+        the kept lists when `lists`, else the hits against the rows' own labels.  A non-uniform
+        `weights` sends the distances to the kernel either way."""
         d, i, kk, idx, skip = self._loo_lists(rows, kmax)
-        dist = d if lists else None
+        dist = d if lists or weights != "uniform" else None
         if self.on_gpu:
             truth = None if lists else self._yd[skip.long()]
             return K.vote_curve_gpu(i, kk, self._yd, kmax, skip=skip, truth=truth, dist=dist,
-                                    hits=hits)
+                                    hits=hits, weights=weights, lists=lists)
         truth = None if lists else self.y[idx]
-        return K.vote_curve_cpu(i, kk, self.y, kmax, skip=skip, truth=truth, dist=dist, hits=hits)
+        return K.vote_curve_cpu(i, kk, self.y, kmax, skip=skip, truth=truth, dist=dist, hits=hits,
+                                weights=weights, lists=lists)
 
     def loo_kneighbors(self, kmax: int, rows=None):
         """(dist, ids) [R, kmax]: the kmax nearest neighbours of the dataset rows `rows` (a slice
@@ -136,24 +146,28 @@ class KNNClassifier(KNNBase):
         _, _, (d, i) = self._loo_batch(slice(None) if rows is None else rows, kmax, lists=True)
         return self._host(d), self._host(i)
 
-    def loo_curve(self, kmax: int, batch_rows: int = 65536):
+    def loo_curve(self, kmax: int, batch_rows: int = 65536, weights: str = "uniform"):
         """(hits int64 [kmax], N): hits[k - 1] = the rows whose k nearest OTHER rows vote their own
-        label — leave-one-out, every k <= kmax from one self-join in batches of batch_rows rows.
-        On a GPU the counts stay on the device over the batches: one copy back at the end."""
+        label (under `weights`, as predict does) — leave-one-out, every k <= kmax from one
+        self-join in batches of batch_rows rows.  On a GPU the counts stay on the device over the
+        batches: one copy back at the end."""
+        K._weight_mode(weights, True)
         kmax = self._loo_kmax(kmax)
         N = self.X.shape[0]
         step = max(1, int(batch_rows))
         hits = None
         for a in range(0, N, step):
-            _, hits, _ = self._loo_batch(slice(a, min(N, a + step)), kmax, lists=False, hits=hits)
+            hits = self._loo_batch(slice(a, min(N, a + step)), kmax, lists=False, hits=hits,
+                                   weights=weights)[1]
         if hits is None:
             return np.zeros(kmax, np.int64), N
         return self._host(hits), N
 
-    def select_k(self, kmax: int):
-        """(best_k, accuracy float64 [kmax]): leave-one-out accuracy of every k <= kmax and the
-        smallest k that reaches the best one (chosen on the integer hit counts)."""
-        hits, N = self.loo_curve(kmax)
+    def select_k(self, kmax: int, weights: str = "uniform"):
+        """(best_k, accuracy float64 [kmax]): leave-one-out accuracy of every k <= kmax under
+        `weights` and the smallest k that reaches the best one (chosen on the integer hit
+        counts)."""
+        hits, N = self.loo_curve(kmax, weights=weights)
         if N == 0:
             raise ValueError("select_k needs a fitted, non-empty dataset")
         return int(np.argmax(hits)) + 1, hits.astype(np.float64) / N

@@ -130,19 +130,36 @@ def _check_kcap(kcap, name: str = "kcap") -> int:
     return kcap
 
 
-def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
+def _curve_weighted(weights, score: bool, have_dist: bool):
+    """The mode of a weighted vote-curve call (validated by _weight_mode), or None for the defaults,
+    which take the unweighted entry."""
+    mode = _weight_mode(weights, have_dist)
+    return mode if (mode or score) else None
+
+
+def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None, *,
+                   weights: str = "uniform", score: bool = False, lists: bool = True):
     """The vote of every prefix of sorted lists (dmlp_cpu_vote_curve): ids [Q, kstride] int32, k
     [Q], labels [N]; skip [Q] drops one id per row (negative: none), entries with id < 0 are
     dropped too.  Returns (labels [Q, kcap] int32 — column j the vote over the first j + 1 kept
     entries, repeated past the last one, -1 for an empty row —, hits int64 [kcap] | None — with
     truth [Q]: rows whose column j equals truth, ADDED to `hits` when one is passed —, (dist, ids)
-    [Q, kcap] | None — with dist: the kept entries, padded with (+inf, -1))."""
+    [Q, kcap] | None — with dist: the kept entries, padded with (+inf, -1)).
+    weights="inv_sqdist" (needs dist) or score=True take dmlp_cpu_vote_curve_weighted: column j is
+    the class with the largest (score, count, label) over the first j + 1 kept entries, a class's
+    score the sum in list order of 1 / d over its entries (d: the engine's SQUARED distances; a row
+    whose first kept entry sits at d == 0 counts the entries at 0 as 1 and every other as 0);
+    score=True appends the winners' scores, float64 [Q, kcap] (uniform: the counts), as a fourth
+    element; lists=False leaves the third None although dist is given (a weighted caller that
+    wants the votes only)."""
+    mode = _curve_weighted(weights, score, dist is not None)
     (ids, k, skip, dist, truth), (Q, ks) = _host_lists(ids, k, skip, dist, (truth,))
     labels = np.ascontiguousarray(labels, np.int32)
     kcap = _check_kcap(kcap)
     lab = np.empty((Q, kcap), np.int32)
-    od = np.empty((Q, kcap), np.float64) if dist is not None else None
-    oi = np.empty((Q, kcap), np.int32) if dist is not None else None
+    lists = bool(lists) and dist is not None
+    od = np.empty((Q, kcap), np.float64) if lists else None
+    oi = np.empty((Q, kcap), np.int32) if lists else None
     if truth is not None:
         if hits is None:
             hits = np.zeros(kcap, np.int64)
@@ -150,11 +167,19 @@ def vote_curve_cpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
             raise ValueError("hits must be a contiguous int64 [kcap] array")
     else:
         hits = None
-    _lib.check(_lib.lib().dmlp_cpu_vote_curve(
+    lists = (od, oi) if lists else None
+    if mode is None:
+        _lib.check(_lib.lib().dmlp_cpu_vote_curve(
+            _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip),
+            labels.ctypes.data, kcap, lab.ctypes.data, _np_ptr(od), _np_ptr(oi), _np_ptr(truth),
+            _np_ptr(hits)), "cpu vote curve")
+        return lab, hits, lists
+    sc = np.empty((Q, kcap), np.float64) if score else None
+    _lib.check(_lib.lib().dmlp_cpu_vote_curve_weighted(
         _np_ptr(dist), ids.ctypes.data, ks, k.ctypes.data, Q, _np_ptr(skip), labels.ctypes.data,
-        kcap, lab.ctypes.data, _np_ptr(od), _np_ptr(oi), _np_ptr(truth), _np_ptr(hits)),
-        "cpu vote curve")
-    return lab, hits, ((od, oi) if dist is not None else None)
+        mode, kcap, lab.ctypes.data, _np_ptr(sc), _np_ptr(od), _np_ptr(oi), _np_ptr(truth),
+        _np_ptr(hits)), "cpu weighted vote curve")
+    return (lab, hits, lists, sc) if score else (lab, hits, lists)
 
 
 VOTE_SCORES_CMAX = 4096  # dmlp_vote_scores_cmax(): classes a score launch takes
@@ -767,20 +792,24 @@ def _device_lists(ids, k, skip, dist, extra_q=()):
     return (ids, per_q[0], per_q[1], dist, *per_q[2:]), (Q, ks)
 
 
-def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None):
-    """vote_curve_cpu on the device (dmlp_vote_curve, csrc/vote_curve.hip): ids [Q, kstride] int32,
-    k / skip / truth [Q] int32, labels [N] int32 and dist (shaped like ids, float64) are torch
-    tensors on one GPU (k may be a host array).  `hits`: an int64 [kcap] tensor there that the
-    counts are ADDED to (a fresh zeroed one when truth is given without it), so a caller can sum
-    over batches of rows without a copy back.  Asynchronous on the current stream."""
+def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, hits=None, *,
+                   weights: str = "uniform", score: bool = False, lists: bool = True):
+    """vote_curve_cpu on the device (dmlp_vote_curve, or dmlp_vote_curve_weighted for a non-uniform
+    `weights` or score=True; csrc/vote_curve.hip): ids [Q, kstride] int32, k / skip / truth [Q]
+    int32, labels [N] int32 and dist (shaped like ids, float64) are torch tensors on one GPU (k may
+    be a host array).  `hits`: an int64 [kcap] tensor there that the counts are ADDED to (a fresh
+    zeroed one when truth is given without it), so a caller can sum over batches of rows without a
+    copy back.  Bit-identical to the CPU's.  Asynchronous on the current stream."""
     torch = _torch()
+    mode = _curve_weighted(weights, score, dist is not None)
     (ids, k, skip, dist, truth), (Q, ks) = _device_lists(ids, k, skip, dist, (truth,))
     dev = ids.device
     labels = _like_ids(labels, ids)
     kcap = _check_kcap(kcap)
     lab = torch.empty((Q, kcap), dtype=torch.int32, device=dev)
-    od = torch.empty((Q, kcap), dtype=torch.float64, device=dev) if dist is not None else None
-    oi = torch.empty((Q, kcap), dtype=torch.int32, device=dev) if dist is not None else None
+    lists = bool(lists) and dist is not None
+    od = torch.empty((Q, kcap), dtype=torch.float64, device=dev) if lists else None
+    oi = torch.empty((Q, kcap), dtype=torch.int32, device=dev) if lists else None
     if truth is not None:
         if hits is None:
             hits = torch.zeros(kcap, dtype=torch.int64, device=dev)
@@ -789,10 +818,17 @@ def vote_curve_gpu(ids, k, labels, kcap: int, skip=None, truth=None, dist=None, 
             raise ValueError("hits must be a contiguous int64 [kcap] tensor on the lists' device")
     else:
         hits = None
-    _lib.check(_lib.lib().dmlp_vote_curve(_p(dist), _p(ids), ks, _p(k), Q, _p(skip), _p(labels),
-                                          kcap, _p(lab), _p(od), _p(oi), _p(truth), _p(hits),
-                                          _stream()), "vote curve")
-    return lab, hits, ((od, oi) if dist is not None else None)
+    lists = (od, oi) if lists else None
+    if mode is None:
+        _lib.check(_lib.lib().dmlp_vote_curve(_p(dist), _p(ids), ks, _p(k), Q, _p(skip),
+                                              _p(labels), kcap, _p(lab), _p(od), _p(oi), _p(truth),
+                                              _p(hits), _stream()), "vote curve")
+        return lab, hits, lists
+    sc = torch.empty((Q, kcap), dtype=torch.float64, device=dev) if score else None
+    _lib.check(_lib.lib().dmlp_vote_curve_weighted(
+        _p(dist), _p(ids), ks, _p(k), Q, _p(skip), _p(labels), mode, kcap, _p(lab), _p(sc), _p(od),
+        _p(oi), _p(truth), _p(hits), _stream()), "weighted vote curve")
+    return (lab, hits, lists, sc) if score else (lab, hits, lists)
 
 
 def vote_scores_gpu(ids, k, labels, label_lo: int, nclass: int, weights: str = "uniform",
