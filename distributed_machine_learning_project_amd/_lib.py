@@ -116,6 +116,12 @@ _SIGS = {
     "dmlp_fallback_select_bytes": (i64, [i32, i64]),
     "dmlp_fallback_select": (i32, [vp, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i32, vp]),
     "dmlp_fallback_topk": (i32, [vp, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i32, vp]),
+    "dmlp_radius_count": (i32, [vp, i64, i32, vp, i32, vp, vp, vp]),
+    "dmlp_radius_fill": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "dmlp_radius_sort_bytes": (i64, [i64, i32]),
+    "dmlp_radius_sort": (i32, [vp, vp, vp, vp, i32, vp, i64, vp]),
+    "dmlp_cpu_radius_count": (i32, [vp, i64, i32, vp, i32, vp, vp, i32]),
+    "dmlp_cpu_radius_fill": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32]),
     "dmlp_merge": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]),
     "dmlp_finalize": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
     "dmlp_vote_curve_kmax": (i32, []),

@@ -217,6 +217,54 @@ extern "C" int dmlp_cpu_knn(const double* X, int64_t N, int A, const double* Qx,
   return 0;
 }
 
+// dmlp_radius_count / dmlp_radius_fill (+ dmlp_radius_sort when sort != 0) on the host: the same
+// distance loop as dmlp_cpu_knn, threaded over the queries, the same bits.
+extern "C" int dmlp_cpu_radius_count(const double* X, int64_t N, int A, const double* Qx, int nq,
+                                     const double* r2, int* out_count, int nthreads) {
+  if (nq <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || !Qx || !r2 || !out_count || (N > 0 && !X)) return -1;
+  parallel_for(nq, default_threads(nthreads), [&](int64_t q) {
+    const double* qv = Qx + q * A;
+    const double r = r2[q];
+    int c = 0;
+    for (int64_t n = 0; n < N; ++n) c += exact_dist(qv, X + n * A, A) <= r ? 1 : 0;
+    out_count[q] = c;
+  });
+  return 0;
+}
+
+extern "C" int dmlp_cpu_radius_fill(const double* X, int64_t N, int A, const double* Qx, int nq,
+                                    const double* r2, const int* count, const int64_t* off,
+                                    double* out_d, int* out_i, int sort, int nthreads) {
+  if (nq <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || !Qx || !r2 || !count || !off || !out_d || !out_i ||
+      (N > 0 && !X))
+    return -1;
+  parallel_for(nq, default_threads(nthreads), [&](int64_t q) {
+    const double* qv = Qx + q * A;
+    const double r = r2[q];
+    const int c = count[q];
+    if (c <= 0) return;
+    // the hits as the device meets them, in ascending id: those past the segment's count (the
+    // largest ids) are dropped; then descending id
+    std::vector<Key> seg;
+    for (int64_t n = 0; n < N && seg.size() < (size_t)c; ++n) {
+      const double d = exact_dist(qv, X + n * A, A);
+      if (d <= r) seg.push_back(Key{d, (int)n});
+    }
+    std::reverse(seg.begin(), seg.end());
+    // slots [count - kept, count): a count larger than the hits leaves the segment's head alone
+    const int64_t o = off[q] + (c - (int64_t)seg.size());
+    if (sort)
+      std::stable_sort(seg.begin(), seg.end(), [](const Key& a, const Key& b) { return a.d < b.d; });
+    for (size_t j = 0; j < seg.size(); ++j) {
+      out_d[o + (int64_t)j] = seg[j].d;
+      out_i[o + (int64_t)j] = seg[j].id;
+    }
+  });
+  return 0;
+}
+
 extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk,
                                  int64_t Q, const int* labels, int* out_label, uint64_t* out_cs) {
   (void)d;

@@ -486,6 +486,40 @@ int dmlp_fallback_select(const double* X, int64_t N, int A, const double* Qx, co
                          const int* qk, int nb, void* ws, int64_t ws_bytes, double* out_d,
                          int* out_i, int kstride, void* stream);
 
+// ---------------------------------------------------------------- device: radius search (radius.hip)
+// Every point within a radius instead of the k nearest.  r2 [nq] is a SQUARED radius, one fp64 per
+// query (no sqrt enters, as everywhere here); point n is a neighbour of query q iff dist(q, x_n) <=
+// r2[q], the boundary inclusive, dist the contract's distance above.  So r2 = +inf keeps every real
+// point (one at distance +inf included), a negative or NaN r2 keeps nothing, r2 = 0 keeps exact
+// duplicates, and a query's neighbours ordered by (dist asc, id desc) are the first count entries
+// of its exact k-NN list at k = count.
+//   dmlp_radius_count: out_count[q] = #{n < N : dist(q, x_n) <= r2[q]}, q < nq.  Writes nq ints,
+//     nothing else.
+//   dmlp_radius_fill: the segment of q = slots off[q] + j, j < count[q], of out_d / out_i receives
+//     its neighbours in DESCENDING id order.  Nothing outside the segments is written.  count is
+//     dmlp_radius_count's output for the same inputs; a hit whose slot would fall outside its
+//     segment is dropped, never written (a count that is too small keeps the smallest ids).  off is
+//     arbitrary: the exclusive prefix sum of count (CSR), or q * stride into lists pre-filled with
+//     (+inf, -1) — the lists dmlp_vote_scores and dmlp_neighbor_means read, with qk = count.
+//   dmlp_radius_sort: every segment reordered to (dist asc, id desc) — a STABLE segmented sort by
+//     distance of the descending-id segments —, in place from the caller's view; segments must not
+//     overlap.  ws: dmlp_radius_sort_bytes(span, nq) bytes, span = max_q(off[q] + count[q]) < 2^31
+//     (-1 otherwise: callers batch).  The segments live on the device, so ws_bytes is the caller's
+//     statement of their span: the sort serves the largest span whose advertised size fits
+//     ws_bytes, and a segment reaching past it is left as it is, never written out of bounds;
+//     fewer bytes than dmlp_radius_sort_bytes(0, nq) return -1.
+// N > INT_MAX, A < 1 or a null pointer (X may be null when N <= 0) return -1 before any launch and
+// write nothing.  nq <= 0 or N <= 0 returns 0; with N <= 0 dmlp_radius_count still writes nq zeros.
+// No atomics: the results do not depend on the schedule.
+int dmlp_radius_count(const double* X, int64_t N, int A, const double* Qx, int nq,
+                      const double* r2, int* out_count, void* stream);
+int dmlp_radius_fill(const double* X, int64_t N, int A, const double* Qx, int nq,
+                     const double* r2, const int* count, const int64_t* off, double* out_d,
+                     int* out_i, void* stream);
+int64_t dmlp_radius_sort_bytes(int64_t span, int nq);
+int dmlp_radius_sort(double* d, int* ids, const int* count, const int64_t* off, int nq, void* ws,
+                     int64_t ws_bytes, void* stream);
+
 // ---------------------------------------------------------------- device: top-k merge (K4)
 // L sorted lists per query (list l of query q at in_*[l*list_stride + q*kin + j]), padded with
 // (+inf, -1); real entries may sit at distance +inf (id >= 0) and rank before the padding; only
@@ -641,6 +675,14 @@ int dmlp_format_report_at(const uint64_t* cs, int nq, int qid_base, int64_t* lin
 // ---------------------------------------------------------------- host (CPU) implementations
 int dmlp_cpu_knn(const double* X, int64_t N, int A, const double* Qx, int64_t Q, const int* qk,
                  int kstride, double* out_d, int* out_i, int nthreads);
+// dmlp_radius_count's and dmlp_radius_fill's contracts on the host, threaded over the queries like
+// dmlp_cpu_knn, the same bits and the same argument checks.  sort = 0: descending-id segments;
+// sort = 1: (dist asc, id desc), what dmlp_radius_sort leaves.
+int dmlp_cpu_radius_count(const double* X, int64_t N, int A, const double* Qx, int nq,
+                          const double* r2, int* out_count, int nthreads);
+int dmlp_cpu_radius_fill(const double* X, int64_t N, int A, const double* Qx, int nq,
+                         const double* r2, const int* count, const int64_t* off, double* out_d,
+                         int* out_i, int sort, int nthreads);
 int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,

@@ -1,7 +1,8 @@
 """What the k-NN estimators share: the fitted rows on the host and, on a GPU, on the device; Update
-records; the exact search (ops.knn.knn_gpu without the fused vote on a GPU, knn_cpu otherwise); and
-the front of every leave-one-out call, which turns dataset rows into queries against the dataset
-itself.  An estimator adds fit(), a one-line _prepare() and the kernels that read the sorted lists
+records; the exact search (ops.knn.knn_gpu without the fused vote on a GPU, knn_cpu otherwise); the
+radius search (radius_count, radius_neighbors, and the padded lists behind the estimators'
+radius_predict); and the front of every leave-one-out call, which turns dataset rows into queries
+against the dataset itself.  An estimator adds fit(), a one-line _prepare() and the kernels that read the sorted lists
 (votes for KNNClassifier, neighbour means for KNNRegressor).
 """
 from __future__ import annotations
@@ -72,6 +73,100 @@ class KNNBase:
         Q = np.ascontiguousarray(Q, np.float64)
         d, i = self._search(Q, self._k(Q, k))
         return self._host(d), self._host(i)
+
+    # ------------------------------------------------------------ radius search
+    # Every point within a radius instead of the k nearest (csrc/radius.hip; dmlp_cpu_radius_* on a
+    # CPU): one count launch over all queries, then fill + sort in contiguous batches of queries.
+    # A query's neighbours under (dist asc, id desc) are the first count_q entries of its k-NN
+    # list, so every radius result equals the k-NN one at the per-query k = count.
+    def _radius_r2(self, Q, radius, r2):
+        """The squared radii float64 [Q] of a radius call: exactly one of radius and r2, a scalar
+        or [Q].  radius: r2 = radius * radius in fp64 (one rounding); negative or NaN raises.  r2
+        passes as it is: a negative or NaN one keeps nothing."""
+        if (radius is None) == (r2 is None):
+            raise ValueError("give exactly one of radius and r2")
+        v = np.asarray(radius if r2 is None else r2, np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != Q.shape[0]):
+            raise ValueError("radius / r2 must be a scalar or [Q]")
+        if r2 is None:
+            if np.isnan(v).any() or (v < 0).any():
+                raise ValueError("radius must be >= 0")
+            with np.errstate(over="ignore"):
+                v = v * v
+        return np.ascontiguousarray(np.broadcast_to(v, (Q.shape[0],)))
+
+    def _radius_front(self, Q, radius, r2):
+        """(queries, squared radii, counts) of a radius call — on the device for a GPU — and the
+        counts on the host."""
+        Q = np.ascontiguousarray(Q, np.float64)
+        if Q.ndim != 2 or Q.shape[1] != self.X.shape[1]:
+            raise ValueError("Q must be [Q, A]")
+        rr = self._radius_r2(Q, radius, r2)
+        if self.on_gpu:
+            torch = _torch()
+            Qd, rd = torch.from_numpy(Q).cuda(), torch.from_numpy(rr).cuda()
+            cd = K.radius_count_gpu(self._ds, Qd, rd)
+            return Qd, rd, cd, cd.cpu().numpy()
+        c = K.radius_count_cpu(self.X, Q, rr)
+        return Q, rr, c, c
+
+    @staticmethod
+    def _radius_batches(count, max_entries, padded):
+        """Contiguous query ranges [a, b) whose entries stay at or below max_entries — the sum of
+        the counts (CSR), or rows x the largest count (padded lists); a single query larger than
+        that is a range of its own."""
+        max_entries = max(1, int(max_entries))
+        a, n = 0, len(count)
+        while a < n:
+            b, tot, cmax = a, 0, 0
+            while b < n:
+                c = int(count[b])
+                size = (b + 1 - a) * max(cmax, c) if padded else tot + c
+                if b > a and size > max_entries:
+                    break
+                tot, cmax, b = tot + c, max(cmax, c), b + 1
+            yield a, b
+            a = b
+
+    def _radius_search(self, Qx, rr, cnt, a, b, sort=True, stride=None):
+        if self.on_gpu:
+            return K.radius_gpu(self._ds, Qx[a:b], rr[a:b], sort=sort, stride=stride, count=cnt[a:b])
+        return K.radius_cpu(self.X, Qx[a:b], rr[a:b], sort=sort, stride=stride, count=cnt[a:b])
+
+    def radius_count(self, Q, radius=None, *, r2=None):
+        """int32 [Q]: the fitted rows within `radius` of each query — or within the SQUARED radius
+        `r2`; exactly one of the two, a scalar or a [Q] array.  The test is dist <= r2 on the
+        engine's squared distances, boundary included; radius is squared in fp64 first (one
+        rounding), so pass r2 where the boundary matters to the bit."""
+        return self._radius_front(Q, radius, r2)[3]
+
+    def radius_neighbors(self, Q, radius=None, *, r2=None, sort_results: bool = True,
+                         max_entries: int = 2 ** 26):
+        """(indptr int64 [Q + 1], dist float64 [total], ids int32 [total]) in CSR: query q's
+        neighbours are slots [indptr[q], indptr[q + 1]), ordered by (dist asc, id desc) — the head
+        of kneighbors' list — or by descending id with sort_results=False.  The queries are worked
+        in contiguous batches of at most max_entries entries (a larger single query is a batch of
+        its own).  Bit-identical on both devices."""
+        Qx, rr, cnt, count = self._radius_front(Q, radius, r2)
+        indptr = np.zeros(len(count) + 1, np.int64)
+        np.cumsum(count, out=indptr[1:])
+        d = np.empty(int(indptr[-1]), np.float64)
+        i = np.empty(int(indptr[-1]), np.int32)
+        for a, b in self._radius_batches(count, max_entries, padded=False):
+            _, bd, bi = self._radius_search(Qx, rr, cnt, a, b, sort=sort_results)
+            d[indptr[a]:indptr[b]] = self._host(bd)
+            i[indptr[a]:indptr[b]] = self._host(bi)
+        return indptr, d, i
+
+    def _radius_lists(self, Q, radius, r2, max_entries):
+        """The sorted neighbours as padded lists, batch by batch: (a, b, dist [b - a, s], ids, count
+        [b - a]) with s the batch's largest count (at least 1) and (b - a) s <= max_entries; on the
+        device for a GPU.  The list kernels read them with k = count."""
+        Qx, rr, cnt, count = self._radius_front(Q, radius, r2)
+        for a, b in self._radius_batches(count, max_entries, padded=True):
+            s = max(1, int(count[a:b].max()))
+            d, i, c = self._radius_search(Qx, rr, cnt, a, b, stride=s)
+            yield a, b, d, i, c
 
     # ------------------------------------------------------------ curves and leave-one-out
     def _curve_kmax(self, kmax):

@@ -13,6 +13,9 @@
     best_k, acc = clf.select_k(kmax)         # the smallest k with the best leave-one-out accuracy
     best_k, acc = clf.select_k(kmax, weights="inv_sqdist")  # ... of the weighted vote (also on
                                              # predict_curve and loo_curve)
+    count = clf.radius_count(Q, radius=r)    # fitted rows within r of each query (or r2=: squared)
+    indptr, dist, ids = clf.radius_neighbors(Q, r2=r2)      # those rows in CSR, (dist asc, id desc)
+    labels = clf.radius_predict(Q, r2=r2)    # == predict(Q, count); also radius_predict_proba
 
 Semantics are the reference's: exact fp64 squared-L2 distances summed left to
 right without FMA, neighbours ordered by (distance asc, id desc).  On a GPU the dataset is
@@ -103,6 +106,39 @@ class KNNClassifier(KNNBase):
         cnt, sc, _ = self._scores(Q, k, weights)
         # only the scores cross back, and the counts when a row's scores sum to 0
         return K.class_proba(self._host(sc), lambda: self._host(cnt))
+
+    # ------------------------------------------------------------ radius votes
+    def _radius_scores(self, Q, radius, r2, weights, max_entries, want):
+        """Per batch of the radius search's padded lists (KNNBase._radius_lists) the class-score
+        kernel at k = count; `want` picks what comes back to the host from (count, score, label)."""
+        K._weight_mode(weights, True)
+        lo, nclass = int(self.classes_[0]), len(self.classes_)
+        out = []
+        for _, _, d, i, c in self._radius_lists(Q, radius, r2, max_entries):
+            if self.on_gpu:
+                res = K.vote_scores_gpu(i, c, self._yd, lo, nclass, weights, dist=d)
+            else:
+                res = K.vote_scores_cpu(i, c, self.y, lo, nclass, weights, dist=d)
+            out.append(want(res))
+        return out
+
+    def radius_predict(self, Q, radius=None, *, r2=None, weights: str = "uniform",
+                       max_entries: int = 2 ** 26):
+        """int32 [Q]: the vote of every fitted row within `radius` (or the squared radius `r2`) of
+        each query — predict(Q, radius_count(Q, ...), weights), bit for bit.  A query without a
+        neighbour predicts -1.  The label range limit is predict_proba's."""
+        out = self._radius_scores(Q, radius, r2, weights, max_entries,
+                                  lambda r: self._host(r[2]))
+        return np.concatenate(out) if out else np.empty(0, np.int32)
+
+    def radius_predict_proba(self, Q, radius=None, *, r2=None, weights: str = "uniform",
+                             max_entries: int = 2 ** 26):
+        """float64 [Q, len(classes_)]: predict_proba over the rows within the radius, bit for bit
+        its result at k = radius_count(Q, ...).  A query without a neighbour is all zeros."""
+        out = self._radius_scores(
+            Q, radius, r2, weights, max_entries,
+            lambda r: K.class_proba(self._host(r[1]), lambda: self._host(r[0])))
+        return np.concatenate(out) if out else np.empty((0, len(self.classes_)), np.float64)
 
     # ------------------------------------------------------------ choosing k
     # The lists are sorted, so the vote for every k <= kmax is a function of one list: one search

@@ -8,6 +8,7 @@
     curve = reg.loo_predict_curve(kmax)      # each dataset row's curve over its nearest OTHER rows
     sse, N = reg.loo_curve(kmax)             # leave-one-out squared error of every k <= kmax
     best_k, mse = reg.select_k(kmax)         # the smallest k with the least leave-one-out error
+    pred = reg.radius_predict(Q, radius=r)   # the mean over the rows within r (or r2=: squared)
 
 The search, update() and the row selection of the leave-one-out calls are KNNClassifier's, from
 _knn_base.KNNBase (exact fp64 squared-L2 distances, neighbours ordered by (distance asc, id
@@ -64,6 +65,22 @@ class KNNRegressor(KNNBase):
         else:
             mean = K.neighbor_means_cpu(i, kk, self.y, weights, dist=d)[0]
         return self._shape(self._host(mean))
+
+    def radius_predict(self, Q, radius=None, *, r2=None, weights: str = "uniform",
+                       max_entries: int = 2 ** 26):
+        """float64 [Q] or [Q, T]: the mean of the targets of every fitted row within `radius` (or
+        the squared radius `r2`) of each query — predict(Q, radius_count(Q, ...), weights), bit
+        for bit.  A query without a neighbour is NaN."""
+        K._weight_mode(weights, True)
+        out = []
+        for _, _, d, i, c in self._radius_lists(Q, radius, r2, max_entries):
+            if self.on_gpu:
+                mean = K.neighbor_means_gpu(i, c, self._yd, weights, dist=d)[0]
+            else:
+                mean = K.neighbor_means_cpu(i, c, self.y, weights, dist=d)[0]
+            out.append(self._host(mean))
+        mean = np.concatenate(out) if out else np.empty((0, self.y.shape[1]), np.float64)
+        return self._shape(mean)
 
     def _curve(self, d, i, kk, kmax, weights, skip=None):
         if self.on_gpu:

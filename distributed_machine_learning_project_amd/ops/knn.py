@@ -18,8 +18,13 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            the uniform / inverse-squared-distance mean of the neighbours' float targets, for the
            whole list or for every prefix of it, in one launch (csrc/neighbor_means.hip):
            KNNRegressor's predict, predict_curve and leave-one-out curves
+  radius_count_gpu / radius_gpu (dmlp_radius_count, dmlp_radius_fill, dmlp_radius_sort)
+           every point within a squared radius instead of the k nearest (csrc/radius.hip): two
+           passes over the exact tier's fp64 distance tile, count then fill, and a stable segmented
+           sort; CSR, or padded lists the list kernels above read with k = count
 CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu,
-vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu.  curve_sse (host, both devices)
+vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu, radius_count_cpu, radius_cpu.
+curve_sse (host, both devices)
 turns a mean curve into squared errors.  The eight list-kernel wrappers check and normalise their
 lists in one place per backend (_host_lists, _device_lists), their weights in _weight_mode and
 their curve length in _check_kcap.
@@ -330,6 +335,88 @@ def merge_cpu(lists_d: np.ndarray, lists_i: np.ndarray, k: np.ndarray, kout: int
                                          k.ctypes.data, Q, d.ctypes.data, i.ctypes.data, kout),
                "cpu merge")
     return d, i
+
+
+RADIUS_SPAN_MAX = (1 << 31) - 1  # slots one fill + sort call addresses (32-bit segment offsets)
+
+
+def _radius_layout(count_max: int, total, Q: int, stride):
+    """The slots a radius fill addresses: `total` (CSR) or (Q - 1) stride + the largest count
+    (padded lists at stride `stride`, which must hold every count), or ValueError."""
+    if stride is None:
+        span = int(total)
+    else:
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        if count_max > stride:
+            raise ValueError(f"a query has {count_max} neighbours: more than stride {stride}")
+        span = (Q - 1) * stride + count_max if Q else 0
+    if span > RADIUS_SPAN_MAX:
+        raise ValueError(f"{span} slots in one radius call: at most {RADIUS_SPAN_MAX}, batch the "
+                         "queries")
+    return span
+
+
+def _radius_host_args(X, Qx, r2):
+    X = np.ascontiguousarray(X, np.float64)
+    Qx = np.ascontiguousarray(Qx, np.float64)
+    if X.ndim != 2 or Qx.ndim != 2 or X.shape[1] != Qx.shape[1] or X.shape[1] < 1:
+        raise ValueError("X must be [N, A] and Qx [Q, A] with A >= 1")
+    r2 = np.asarray(r2, np.float64)
+    if r2.ndim == 0:
+        r2 = np.full(Qx.shape[0], float(r2), np.float64)
+    r2 = np.ascontiguousarray(r2)
+    if r2.shape != (Qx.shape[0],):
+        raise ValueError("r2 must be a scalar or [Q]")
+    return X, Qx, r2
+
+
+def radius_count_cpu(X, Qx, r2, nthreads: int = 0):
+    """int32 [Q]: the points of X [N, A] within the SQUARED radius r2 (a scalar or [Q] float64) of
+    each query row of Qx [Q, A], the boundary included (dmlp_cpu_radius_count): dist(q, x) <= r2_q
+    in the engine's distance.  A negative or NaN r2 counts nothing, +inf every point."""
+    X, Qx, r2 = _radius_host_args(X, Qx, r2)
+    Q = Qx.shape[0]
+    count = np.zeros(Q, np.int32)
+    _lib.check(_lib.lib().dmlp_cpu_radius_count(
+        X.ctypes.data if X.size else None, X.shape[0], X.shape[1], Qx.ctypes.data, Q,
+        r2.ctypes.data, count.ctypes.data, nthreads), "cpu radius count")
+    return count
+
+
+def radius_cpu(X, Qx, r2, sort: bool = True, stride=None, count=None, nthreads: int = 0):
+    """Every point within the squared radius r2 of each query (dmlp_cpu_radius_fill), ordered by
+    (dist asc, id desc) — the first count_q entries of the query's exact k-NN list — or, with
+    sort=False, by descending id.  stride=None: CSR (indptr int64 [Q + 1], dist float64 [total],
+    ids int32 [total]).  stride=s: padded lists (dist [Q, s], ids [Q, s], count int32 [Q]), slots
+    past count_q holding (+inf, -1): what vote_scores_cpu and neighbor_means_cpu read with k =
+    count; a count above s is a ValueError.  count: radius_count_cpu's result for the same
+    arguments, when the caller has it."""
+    X, Qx, r2 = _radius_host_args(X, Qx, r2)
+    Q = Qx.shape[0]
+    if count is None:
+        count = radius_count_cpu(X, Qx, r2, nthreads)
+    count = np.ascontiguousarray(count, np.int32)
+    if count.shape != (Q,):
+        raise ValueError("count must be [Q]")
+    indptr = np.zeros(Q + 1, np.int64)
+    np.cumsum(count, out=indptr[1:])
+    _radius_layout(int(count.max()) if Q else 0, indptr[Q], Q, stride)
+    if stride is None:
+        off = indptr[:Q]
+        d = np.empty(int(indptr[Q]), np.float64)
+        i = np.empty(int(indptr[Q]), np.int32)
+    else:
+        off = np.arange(Q, dtype=np.int64) * int(stride)
+        d = np.full((Q, int(stride)), np.inf, np.float64)
+        i = np.full((Q, int(stride)), -1, np.int32)
+    if d.size:
+        _lib.check(_lib.lib().dmlp_cpu_radius_fill(
+            X.ctypes.data if X.size else None, X.shape[0], X.shape[1], Qx.ctypes.data, Q,
+            r2.ctypes.data, count.ctypes.data, np.ascontiguousarray(off).ctypes.data,
+            d.ctypes.data, i.ctypes.data, 1 if sort else 0, nthreads), "cpu radius fill")
+    return (indptr, d, i) if stride is None else (d, i, count)
 
 
 # ======================================================================= GPU backend
@@ -896,6 +983,89 @@ def neighbor_means_curve_gpu(ids, k, targets, kcap: int, weights: str = "uniform
                                                     _p(targets), T, mode, kcap, _p(mean),
                                                     _stream()), "neighbor means curve")
     return mean
+
+
+# ---------------------------------------------------------------- radius search
+def _radius_device_args(ds, Qx, r2):
+    """(Qx, r2) of a device radius call: Qx a float64 [Q, A] tensor on the dataset's GPU (strided
+    is fine), r2 a scalar, a host array or a tensor, float64 [Q] there afterwards.  ValueError for
+    anything else."""
+    torch = _torch()
+    dev = ds.X.device
+    if not torch.is_tensor(Qx) or Qx.dtype != torch.float64 or Qx.dim() != 2 or \
+            Qx.shape[1] != ds.A or Qx.device != dev:
+        raise ValueError("Qx must be a float64 [Q, A] tensor on the dataset's device")
+    if ds.A < 1:
+        raise ValueError("the dataset has no attributes")
+    Q = Qx.shape[0]
+    if torch.is_tensor(r2):
+        if r2.dtype != torch.float64 or r2.device != dev:
+            raise ValueError("r2 must be a float64 tensor on the dataset's device")
+    else:
+        r2 = np.asarray(r2, np.float64)
+        if r2.ndim == 0:
+            r2 = np.full(Q, float(r2), np.float64)
+        r2 = torch.from_numpy(np.ascontiguousarray(r2)).to(dev)
+    if tuple(r2.shape) != (Q,):
+        raise ValueError("r2 must be a scalar or [Q]")
+    return Qx.contiguous(), r2.contiguous()
+
+
+def radius_count_gpu(ds: DeviceDataset, Qx, r2):
+    """radius_count_cpu on the device (dmlp_radius_count, csrc/radius.hip): ds the prepared
+    dataset, Qx a float64 [Q, A] tensor on its GPU, r2 the SQUARED radii (a scalar, a host array
+    or a float64 [Q] tensor there).  Returns an int32 [Q] tensor there, the CPU's numbers.
+    Asynchronous on the current stream."""
+    torch = _torch()
+    Qx, r2 = _radius_device_args(ds, Qx, r2)
+    Q = Qx.shape[0]
+    count = torch.zeros(Q, dtype=torch.int32, device=Qx.device)
+    _lib.check(_lib.lib().dmlp_radius_count(_p(ds.X) if ds.N else None, ds.N, ds.A, _p(Qx), Q,
+                                            _p(r2), _p(count), _stream()), "radius count")
+    return count
+
+
+def radius_gpu(ds: DeviceDataset, Qx, r2, sort: bool = True, stride=None, count=None):
+    """radius_cpu on the device (dmlp_radius_fill, then dmlp_radius_sort unless sort=False):
+    arguments as for radius_count_gpu, count its result when the caller has it.  stride=None: CSR
+    (indptr int64 [Q + 1], dist [total], ids [total]) as tensors on the GPU, the prefix sum a
+    torch.cumsum; stride=s: padded (dist [Q, s], ids [Q, s], count), pre-filled with (+inf, -1),
+    which vote_scores_gpu and neighbor_means_gpu read with k = count.  Bit-identical to the CPU's.
+    One host sync for the sizes (the total, or the largest count); a count above s or more than
+    2^31 - 1 slots raise ValueError: callers batch."""
+    torch = _torch()
+    L = _lib.lib()
+    Qx, r2 = _radius_device_args(ds, Qx, r2)
+    Q = Qx.shape[0]
+    dev = Qx.device
+    if count is None:
+        count = radius_count_gpu(ds, Qx, r2)
+    if not torch.is_tensor(count) or count.dtype != torch.int32 or tuple(count.shape) != (Q,) \
+            or count.device != dev:
+        raise ValueError("count must be an int32 [Q] tensor on the dataset's device")
+    count = count.contiguous()
+    if stride is None:
+        indptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(count, 0, out=indptr[1:])
+        total = int(indptr[Q].item()) if Q else 0
+        span = _radius_layout(0, total, Q, None)
+        off = indptr[:Q]
+        d = torch.empty(total, dtype=torch.float64, device=dev)
+        i = torch.empty(total, dtype=torch.int32, device=dev)
+    else:
+        span = _radius_layout(int(count.max().item()) if Q else 0, 0, Q, stride)
+        off = torch.arange(Q, dtype=torch.int64, device=dev) * int(stride)
+        d = torch.full((Q, int(stride)), float("inf"), dtype=torch.float64, device=dev)
+        i = torch.full((Q, int(stride)), -1, dtype=torch.int32, device=dev)
+    if Q and span and ds.N:
+        _lib.check(L.dmlp_radius_fill(_p(ds.X), ds.N, ds.A, _p(Qx), Q, _p(r2), _p(count), _p(off),
+                                      _p(d), _p(i), _stream()), "radius fill")
+        if sort:
+            nbytes = L.dmlp_radius_sort_bytes(span, Q)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.dmlp_radius_sort(_p(d), _p(i), _p(count), _p(off), Q, _p(ws), nbytes,
+                                          _stream()), "radius sort")
+    return (indptr, d, i) if stride is None else (d, i, count)
 
 
 # ---------------------------------------------------------------- report text on the GPU

@@ -31,6 +31,29 @@ def topk(X: np.ndarray, q: np.ndarray, k: int):
     return d[order], ids[order].astype(np.int64)
 
 
+def radius_reference(X, Qx, r2, sort: bool = True):
+    """Radius search in NumPy float64: per query the points with distances(X, q) <= r2_q (r2 a
+    SQUARED radius, a scalar or [Q]; the boundary included, so a negative or NaN r2 keeps nothing
+    and +inf everything), ordered by (dist asc, id desc), or by descending id with sort=False.
+    Returns CSR (indptr int64 [Q + 1], dist float64 [total], ids int32 [total])."""
+    X = np.asarray(X, np.float64)
+    Qx = np.asarray(Qx, np.float64)
+    r2 = np.broadcast_to(np.asarray(r2, np.float64), (Qx.shape[0],))
+    indptr, ds, ids = [0], [], []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q in range(Qx.shape[0]):
+            d = distances(X, Qx[q])
+            hit = np.flatnonzero(d <= r2[q])[::-1]           # descending id
+            if sort:
+                hit = hit[np.argsort(d[hit], kind="stable")]  # stable: id desc among equals
+            ds.append(d[hit])
+            ids.append(hit.astype(np.int32))
+            indptr.append(indptr[-1] + len(hit))
+    return (np.asarray(indptr, np.int64),
+            np.concatenate(ds) if ds else np.empty(0, np.float64),
+            np.concatenate(ids) if ids else np.empty(0, np.int32))
+
+
 def vote(ids, labels) -> int:
     if len(ids) == 0:
         return -1
