@@ -277,51 +277,6 @@ extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, c
   return 0;
 }
 
-extern "C" int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int* qk,
-                                   int64_t Q, const int* skip, const int* labels, int kcap,
-                                   int* out_label, double* out_d, int* out_i, const int* truth,
-                                   unsigned long long* hits) {
-  if (Q <= 0) return 0;
-  if (kcap < 1 || kcap > 256 || kstride < 1) return -1;
-  if ((out_d == nullptr) != (out_i == nullptr) || (truth == nullptr) != (hits == nullptr))
-    return -1;
-  if (out_d && !d) return -1;
-  std::unordered_map<int, int> cnt;
-  for (int64_t q = 0; q < Q; ++q) {
-    const int* iq = ids + q * kstride;
-    int* ol = out_label + q * kcap;
-    const int n = std::min(std::min(qk[q], kstride), 256);
-    const int sk = skip ? skip[q] : -1;
-    cnt.clear();
-    int m = 0, best = -1, bc = 0;  // the running vote: a count only ever grows by one
-    for (int e = 0; e < n && m < kcap; ++e) {
-      const int id = iq[e];
-      if (id < 0 || id == sk) continue;
-      const int lb = labels[id];
-      const int c = ++cnt[lb];
-      if (c > bc || (c == bc && lb > best)) {
-        bc = c;
-        best = lb;
-      }
-      if (out_i) {
-        out_i[q * kcap + m] = id;
-        out_d[q * kcap + m] = d[q * kstride + e];
-      }
-      ol[m++] = best;
-    }
-    for (int j = m; j < kcap; ++j) {
-      ol[j] = m ? ol[m - 1] : -1;
-      if (out_i) {
-        out_i[q * kcap + j] = -1;
-        out_d[q * kcap + j] = INFINITY;
-      }
-    }
-    if (hits)
-      for (int j = 0; j < kcap; ++j) hits[j] += ol[j] == truth[q];
-  }
-  return 0;
-}
-
 extern "C" int dmlp_cpu_vote_curve_weighted(const double* d, const int* ids, int kstride,
                                             const int* qk, int64_t Q, const int* skip,
                                             const int* labels, int mode, int kcap, int* out_label,
@@ -385,6 +340,16 @@ extern "C" int dmlp_cpu_vote_curve_weighted(const double* d, const int* ids, int
       for (int j = 0; j < kcap; ++j) hits[j] += ol[j] == truth[q];
   }
   return 0;
+}
+
+// The uniform curve is mode 0 without the score column: there s == c, so (s, c, label) orders
+// like (c, label).
+extern "C" int dmlp_cpu_vote_curve(const double* d, const int* ids, int kstride, const int* qk,
+                                   int64_t Q, const int* skip, const int* labels, int kcap,
+                                   int* out_label, double* out_d, int* out_i, const int* truth,
+                                   unsigned long long* hits) {
+  return dmlp_cpu_vote_curve_weighted(d, ids, kstride, qk, Q, skip, labels, 0, kcap, out_label,
+                                      nullptr, out_d, out_i, truth, hits);
 }
 
 extern "C" int dmlp_cpu_vote_scores(const double* d, const int* ids, int kstride, const int* qk,

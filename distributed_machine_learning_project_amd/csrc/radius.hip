@@ -2,10 +2,8 @@
 // fp64 per query, the boundary inclusive), d the reference's fp64 distance (engine.cpp:12-18: left
 // to right over the attributes, each subtraction, product and sum separately rounded — no FMA).
 //
-// Two passes over exact.hip's distance tile (k_exact_topk: 256 threads = 64 queries, the data
-// stream tiled by 128 points, thread (tx = tid & 15, ty = tid >> 4) owning queries ty + 16 i and
-// points tx + 16 j of the tile, chunks staged in LDS behind a software-pipelined fetch, two
-// attributes per step) with none of its selection: no candidate buffers, no moving threshold, no
+// Two passes over the distance tile k_exact_topk uses (fp64_tile.h: 64 queries x 128 points per
+// workgroup) with none of its selection: no candidate buffers, no moving threshold, no
 // compaction.  A query's 16 threads sit in ONE wave, so both passes are deterministic without LDS
 // buffers and without atomics:
 //   count  every lane counts its own hits per row; one 16-lane reduction at the end.
@@ -20,28 +18,21 @@
 #include <hipcub/hipcub.hpp>
 
 #include "dmlp.h"
-#include "dmlp_device.h"
+#include "fp64_tile.h"
 #include <limits.h>
 #include <math.h>
 
 namespace {
 
 // exact.hip's ExK16 tile without the buffers: 64 queries x 128 points, 16 attributes per chunk
-struct Rd {
-  static constexpr int QB = 64, PJ = 8, PT = 16 * PJ, AC = 16;
-  static constexpr int AS = AC + 2;   // LDS row stride in doubles: 16-byte aligned rows (b128)
-  static constexpr int RI = QB / 16;  // rows (queries) per thread
-  static constexpr int NQ = (QB * AC + 255) / 256, NX = (PT * AC + 255) / 256;
-  static constexpr int LDS = (QB + PT) * AS * 8;
-};
+using Rd = dmlp::Fp64Tile<64, 8, 16>;
 
 template <bool FILL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_radius(
     const double* __restrict__ X, int64_t N, int A, const double* __restrict__ Qx, int nq,
     const double* __restrict__ r2, const int* __restrict__ count, const int64_t* __restrict__ off,
     int* __restrict__ out_count, double* __restrict__ out_d, int* __restrict__ out_i) {
-  constexpr int QB = Rd::QB, PJ = Rd::PJ, PT = Rd::PT, AC = Rd::AC, AS = Rd::AS;
-  constexpr int RI = Rd::RI, NQ = Rd::NQ, NX = Rd::NX;
+  constexpr int QB = Rd::QB, PJ = Rd::PJ, PT = Rd::PT, AS = Rd::AS, RI = Rd::RI;
   __shared__ __attribute__((aligned(16))) double Qs[QB][AS];
   __shared__ __attribute__((aligned(16))) double Xs[PT][AS];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -66,103 +57,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const unsigned below = (1u << tx) - 1u;       // the row's lanes before this one
   const int fshift = ((tid & 63) >> 4) << 4;    // the row's 16-bit field of a ballot
 
-  // staging is software-pipelined: the next (tile, chunk)'s elements are loaded into registers
-  // while the current chunk computes, so no wave waits on global memory at the barriers
-  double qr[NQ], xr[NX];
-  auto fetch = [&](int64_t p0, int a0) __attribute__((always_inline)) {
-    const int ac = A - a0 < AC ? A - a0 : AC;
+  dmlp::fp64_tile_scan<Rd>(
+      X, N, A, Qx, q0, nq, Qs, Xs, [](int qi) { return qi; },
+      [&](int64_t p0, const double (&acc)[RI][PJ]) __attribute__((always_inline)) {
+        // offer the tile's distances, one point column per round (<= 16 per query per round);
+        // pad points of the last tile (p >= N) are no hits, with r2 = +inf too
 #pragma unroll
-    for (int u = 0; u < NQ; ++u) {
-      const int e = tid + 256 * u, r = e / AC, a = e % AC;
-      const int qi = q0 + r;
-      qr[u] = (e < QB * AC && qi < nq && a < ac) ? Qx[(int64_t)qi * A + a0 + a] : 0.0;
-    }
+        for (int j = 0; j < PJ; ++j) {
+          const int64_t p = p0 + tx + 16 * j;
 #pragma unroll
-    for (int u = 0; u < NX; ++u) {
-      const int e = tid + 256 * u, r = e / AC, a = e % AC;
-      const int64_t pi = p0 + r;
-      xr[u] = (e < PT * AC && pi < N && a < ac) ? X[pi * A + a0 + a] : 0.0;
-    }
-  };
-  fetch(0, 0);
-  for (int64_t p0 = 0; p0 < N; p0 += PT) {
-    double acc[RI][PJ];
-#pragma unroll
-    for (int i = 0; i < RI; ++i)
-#pragma unroll
-      for (int j = 0; j < PJ; ++j) acc[i][j] = 0.0;
-    for (int a0 = 0; a0 < A; a0 += AC) {
-      const int ac = A - a0 < AC ? A - a0 : AC;
-      __syncthreads();  // the previous chunk's reads are done
-#pragma unroll
-      for (int u = 0; u < NQ; ++u)
-        if (tid + 256 * u < QB * AC) Qs[(tid + 256 * u) / AC][(tid + 256 * u) % AC] = qr[u];
-#pragma unroll
-      for (int u = 0; u < NX; ++u)
-        if (tid + 256 * u < PT * AC) Xs[(tid + 256 * u) / AC][(tid + 256 * u) % AC] = xr[u];
-      __syncthreads();
-      {
-        int64_t np = p0;
-        int na = a0 + AC;
-        if (na >= A) { na = 0; np = p0 + PT; }
-        if (np < N) fetch(np, na);
-      }
-      // two attributes per step: 16-byte LDS reads; the sums stay in attribute order
-      int a = 0;
-      for (; a + 1 < ac; a += 2) {
-        double2 qv[RI], xv[PJ];
-#pragma unroll
-        for (int i = 0; i < RI; ++i) qv[i] = *(const double2*)&Qs[ty + 16 * i][a];
-#pragma unroll
-        for (int j = 0; j < PJ; ++j) xv[j] = *(const double2*)&Xs[tx + 16 * j][a];
-#pragma unroll
-        for (int i = 0; i < RI; ++i)
-#pragma unroll
-          for (int j = 0; j < PJ; ++j) {
-            const double d0 = __dsub_rn(qv[i].x, xv[j].x);
-            acc[i][j] = __dadd_rn(acc[i][j], __dmul_rn(d0, d0));
-            const double d1 = __dsub_rn(qv[i].y, xv[j].y);
-            acc[i][j] = __dadd_rn(acc[i][j], __dmul_rn(d1, d1));
+          for (int i = 0; i < RI; ++i) {
+            const bool hit = p < N && acc[i][j] <= rq[i];
+            if (!FILL) {
+              hits[i] += hit ? 1 : 0;
+            } else {
+              // every lane of the wave reaches the ballot: it stands outside the divergent write
+              const unsigned field = (unsigned)(__ballot(hit) >> fshift) & 0xffffu;
+              const int slot = hits[i] - 1 - __popc(field & below);
+              if (hit && slot >= 0) {  // a hit past the segment's count is dropped, never written
+                out_d[base[i] + slot] = acc[i][j];
+                out_i[base[i] + slot] = (int)p;
+              }
+              hits[i] -= __popc(field);
+            }
           }
-      }
-      if (a < ac) {  // odd attribute count: the last one alone
-        double qv[RI], xv[PJ];
-#pragma unroll
-        for (int i = 0; i < RI; ++i) qv[i] = Qs[ty + 16 * i][a];
-#pragma unroll
-        for (int j = 0; j < PJ; ++j) xv[j] = Xs[tx + 16 * j][a];
-#pragma unroll
-        for (int i = 0; i < RI; ++i)
-#pragma unroll
-          for (int j = 0; j < PJ; ++j) {
-            const double d0 = __dsub_rn(qv[i], xv[j]);
-            acc[i][j] = __dadd_rn(acc[i][j], __dmul_rn(d0, d0));
-          }
-      }
-    }
-    // offer the tile's distances, one point column per round (<= 16 per query per round); pad
-    // points of the last tile (p >= N) are no hits, with r2 = +inf too
-#pragma unroll
-    for (int j = 0; j < PJ; ++j) {
-      const int64_t p = p0 + tx + 16 * j;
-#pragma unroll
-      for (int i = 0; i < RI; ++i) {
-        const bool hit = p < N && acc[i][j] <= rq[i];
-        if (!FILL) {
-          hits[i] += hit ? 1 : 0;
-        } else {
-          // every lane of the wave reaches the ballot: it stands outside the divergent write
-          const unsigned field = (unsigned)(__ballot(hit) >> fshift) & 0xffffu;
-          const int slot = hits[i] - 1 - __popc(field & below);
-          if (hit && slot >= 0) {   // a hit past the segment's count is dropped, never written
-            out_d[base[i] + slot] = acc[i][j];
-            out_i[base[i] + slot] = (int)p;
-          }
-          hits[i] -= __popc(field);
         }
-      }
-    }
-  }
+      });
   if (!FILL) {
 #pragma unroll
     for (int i = 0; i < RI; ++i) {
