@@ -122,6 +122,9 @@ _SIGS = {
     "dmlp_radius_sort": (i32, [vp, vp, vp, vp, i32, vp, i64, vp]),
     "dmlp_cpu_radius_count": (i32, [vp, i64, i32, vp, i32, vp, vp, i32]),
     "dmlp_cpu_radius_fill": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32]),
+    "dmlp_radius_components": (i32, [vp, i64, i32, C.c_double, vp, vp, vp]),
+    "dmlp_set_components_order": (i32, [i32]),
+    "dmlp_cpu_radius_components": (i32, [vp, i64, i32, C.c_double, vp, i32]),
     "dmlp_merge": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]),
     "dmlp_finalize": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
     "dmlp_vote_curve_kmax": (i32, []),

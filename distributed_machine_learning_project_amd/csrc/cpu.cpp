@@ -265,6 +265,41 @@ extern "C" int dmlp_cpu_radius_fill(const double* X, int64_t N, int A, const dou
   return 0;
 }
 
+// dmlp_radius_components on the host: the device's union-find (hook the larger root under the
+// smaller by compare-exchange, so parent[x] <= x and a tree's root is its smallest id), threaded
+// over the rows of the lower triangle; the flatten runs in ascending id, where a row's parent
+// already holds its root.  The same integers as the device's.
+extern "C" int dmlp_cpu_radius_components(const double* X, int64_t N, int A, double r2, int* comp,
+                                          int nthreads) {
+  if (N <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || !X || !comp) return -1;
+  for (int64_t i = 0; i < N; ++i) comp[i] = (int)i;
+  parallel_for(N, default_threads(nthreads), [&](int64_t q) {
+    const double* qv = X + q * A;
+    int cur = (int)q;  // the last root seen for q: an ancestor of q for good
+    for (int64_t p = 0; p < q; ++p) {
+      if (!(exact_dist(qv, X + p * A, A) <= r2)) continue;
+      int a = cur, b = (int)p;
+      while (a != b) {
+        if (a < b) std::swap(a, b);
+        const int pa = __atomic_load_n(comp + a, __ATOMIC_RELAXED);
+        if (pa != a) { a = pa; continue; }
+        const int pb = __atomic_load_n(comp + b, __ATOMIC_RELAXED);
+        if (pb != b) { b = pb; continue; }
+        int seen = a;
+        if (__atomic_compare_exchange_n(comp + a, &seen, b, false, __ATOMIC_RELAXED,
+                                        __ATOMIC_RELAXED))
+          a = b;
+        else
+          a = seen;
+      }
+      cur = a;
+    }
+  });
+  for (int64_t i = 0; i < N; ++i) comp[i] = comp[comp[i]];
+  return 0;
+}
+
 extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk,
                                  int64_t Q, const int* labels, int* out_label, uint64_t* out_cs) {
   (void)d;

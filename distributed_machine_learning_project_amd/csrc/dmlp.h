@@ -520,6 +520,32 @@ int64_t dmlp_radius_sort_bytes(int64_t span, int nq);
 int dmlp_radius_sort(double* d, int* ids, const int* count, const int64_t* off, int nq, void* ws,
                      int64_t ws_bytes, void* stream);
 
+// ---------------------------------------------------------------- device: radius-graph components (components.hip)
+// G is the graph on rows 0 .. N - 1 of X with an edge {i, j} iff dist(x_i, x_j) <= r2: dist the
+// contract's distance above, symmetric bit for bit ((a - b) and (b - a) differ in sign only); r2
+// ONE squared radius, an fp64 scalar, the boundary inclusive.  A negative or NaN r2 links nothing
+// (comp[i] = i); r2 = +inf links every pair of rows, a pair at distance +inf included.
+//   comp[i] = the smallest row id in i's connected component of G
+// so comp[i] <= i, comp[comp[i]] == comp[i] and comp[0] == 0.  A pure function of the inputs: no
+// run-to-run variation, although a lock-free union-find on comp[] (atomics) builds it.  Three
+// launches on `stream`, no workspace; only the lower triangle of the distances is computed (half
+// the work of a dmlp_radius_count over the rows).  *status (one device word) is 0 afterwards; 1
+// says that a union or a walk overran its step bound (2 N + 64), which cannot happen while
+// parent <= child holds: a defect reported instead of a hang, comp is then not to be used.
+// DBSCAN(r2, min_samples) on top of it (models/dbscan.py): row i is a core row iff #{n : dist(x_i,
+// x_n) <= r2} >= min_samples (the row itself counts: dmlp_radius_count); clusters are the
+// components of G restricted to the core rows, numbered 0 .. C - 1 in ascending order of their
+// smallest core row id; a non-core row with a core row within r2 is a border row and takes the
+// cluster of its nearest core row under (dist asc, id desc) (dmlp_exact_topk at k = 1); every
+// other row is noise, -1.
+// N <= 0 returns 0 and writes nothing; N > INT_MAX, A < 1 or a null X, comp or status return -1
+// before any launch; a launch failure returns -(int)hipError.
+int dmlp_radius_components(const double* X, int64_t N, int A, double r2, int* comp /*[N]*/,
+                           int* status /*1 device word*/, void* stream);
+// A/B switch of tools/components_bench.py: 1 (the default) starts the link kernel's workgroups
+// heaviest first, 0 in row order; the results are the same.  Returns the previous value.
+int dmlp_set_components_order(int heavy_first);
+
 // ---------------------------------------------------------------- device: top-k merge (K4)
 // L sorted lists per query (list l of query q at in_*[l*list_stride + q*kin + j]), padded with
 // (+inf, -1); real entries may sit at distance +inf (id >= 0) and rank before the padding; only
@@ -683,6 +709,10 @@ int dmlp_cpu_radius_count(const double* X, int64_t N, int A, const double* Qx, i
 int dmlp_cpu_radius_fill(const double* X, int64_t N, int A, const double* Qx, int nq,
                          const double* r2, const int* count, const int64_t* off, double* out_d,
                          int* out_i, int sort, int nthreads);
+// dmlp_radius_components' contract on the host (no status: its walks need no bound), the same
+// integers and the same argument checks.
+int dmlp_cpu_radius_components(const double* X, int64_t N, int A, double r2, int* comp,
+                               int nthreads);
 int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,

@@ -13,6 +13,21 @@ from ..ops import knn as K
 from ..ops.knn import _torch
 
 
+def squared_radius(radius, r2, name: str = "radius"):
+    """The squared radius (float64, shaped like the argument) of a call that takes exactly one of a
+    radius and r2.  radius: r2 = radius * radius in fp64 (one rounding); negative or NaN raises.
+    r2 passes as it is: a negative or NaN one keeps nothing."""
+    if (radius is None) == (r2 is None):
+        raise ValueError(f"give exactly one of {name} and r2")
+    v = np.asarray(radius if r2 is None else r2, np.float64)
+    if r2 is None:
+        if np.isnan(v).any() or (v < 0).any():
+            raise ValueError(f"{name} must be >= 0")
+        with np.errstate(over="ignore"):
+            v = v * v
+    return v
+
+
 class KNNBase:
     def __init__(self, device: str = "auto", exact: bool = False, cpu_method: str = "brute"):
         self.on_gpu = device == "gpu" or (device == "auto" and _torch().cuda.is_available())
@@ -83,16 +98,9 @@ class KNNBase:
         """The squared radii float64 [Q] of a radius call: exactly one of radius and r2, a scalar
         or [Q].  radius: r2 = radius * radius in fp64 (one rounding); negative or NaN raises.  r2
         passes as it is: a negative or NaN one keeps nothing."""
-        if (radius is None) == (r2 is None):
-            raise ValueError("give exactly one of radius and r2")
-        v = np.asarray(radius if r2 is None else r2, np.float64)
+        v = squared_radius(radius, r2)
         if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != Q.shape[0]):
             raise ValueError("radius / r2 must be a scalar or [Q]")
-        if r2 is None:
-            if np.isnan(v).any() or (v < 0).any():
-                raise ValueError("radius must be >= 0")
-            with np.errstate(over="ignore"):
-                v = v * v
         return np.ascontiguousarray(np.broadcast_to(v, (Q.shape[0],)))
 
     def _radius_front(self, Q, radius, r2):

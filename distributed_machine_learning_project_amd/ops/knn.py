@@ -22,8 +22,13 @@ engine.h drop-in run as well — no part of a call is orchestrated from Python:
            every point within a squared radius instead of the k nearest (csrc/radius.hip): two
            passes over the exact tier's fp64 distance tile, count then fill, and a stable segmented
            sort; CSR, or padded lists the list kernels above read with k = count
+  radius_components_gpu (dmlp_radius_components)  connected components of the graph "within one
+           squared radius" (csrc/components.hip): the same tile over the lower triangle of the rows
+           against themselves, its hits united in a lock-free union-find as they appear; with
+           exact_nearest_gpu (dmlp_exact_topk at k = 1 on raw device rows) what models.DBSCAN runs
 CPU: libdmlp's threaded brute force (or the KD-tree of bench.debug), vote_curve_cpu,
-vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu, radius_count_cpu, radius_cpu.
+vote_scores_cpu, neighbor_means_cpu, neighbor_means_curve_cpu, radius_count_cpu, radius_cpu,
+radius_components_cpu.
 curve_sse (host, both devices)
 turns a mean curve into squared errors.  The eight list-kernel wrappers check and normalise their
 lists in one place per backend (_host_lists, _device_lists), their weights in _weight_mode and
@@ -417,6 +422,28 @@ def radius_cpu(X, Qx, r2, sort: bool = True, stride=None, count=None, nthreads: 
             r2.ctypes.data, count.ctypes.data, np.ascontiguousarray(off).ctypes.data,
             d.ctypes.data, i.ctypes.data, 1 if sort else 0, nthreads), "cpu radius fill")
     return (indptr, d, i) if stride is None else (d, i, count)
+
+
+def _components_r2(r2) -> float:
+    try:
+        return float(r2)
+    except (TypeError, ValueError):
+        raise ValueError("r2 must be one float, the SQUARED radius") from None
+
+
+def radius_components_cpu(X, r2, nthreads: int = 0):
+    """int32 [N]: comp[i] = the smallest row id in the connected component of row i of X [N, A]
+    under the edges dist(x_i, x_j) <= r2 (dmlp_cpu_radius_components) — r2 ONE squared radius, the
+    boundary included; a negative or NaN r2 links nothing, +inf every pair."""
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("X must be [N, A] with A >= 1")
+    comp = np.empty(X.shape[0], np.int32)
+    if X.shape[0]:
+        _lib.check(_lib.lib().dmlp_cpu_radius_components(
+            X.ctypes.data, X.shape[0], X.shape[1], _components_r2(r2), comp.ctypes.data, nthreads),
+            "cpu radius components")
+    return comp
 
 
 # ======================================================================= GPU backend
@@ -1066,6 +1093,59 @@ def radius_gpu(ds: DeviceDataset, Qx, r2, sort: bool = True, stride=None, count=
             _lib.check(L.dmlp_radius_sort(_p(d), _p(i), _p(count), _p(off), Q, _p(ws), nbytes,
                                           _stream()), "radius sort")
     return (indptr, d, i) if stride is None else (d, i, count)
+
+
+# ---------------------------------------------------------------- radius-graph components
+def _device_rows(X, name: str = "X"):
+    torch = _torch()
+    if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or not X.is_cuda or \
+            X.shape[1] < 1:
+        raise ValueError(f"{name} must be a float64 [N, A] tensor on a GPU with A >= 1")
+    return X.contiguous()
+
+
+def radius_components_gpu(X, r2):
+    """radius_components_cpu on the device (dmlp_radius_components, csrc/components.hip): X a
+    float64 [N, A] tensor on a GPU (strided is fine), r2 a Python float.  Returns an int32 [N]
+    tensor there, the CPU's integers.  One host sync, for the status word: a union-find walk that
+    overran its bound raises RuntimeError."""
+    torch = _torch()
+    X = _device_rows(X)
+    r2 = _components_r2(r2)
+    N = X.shape[0]
+    comp = torch.empty(N, dtype=torch.int32, device=X.device)
+    if N:
+        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+        _lib.check(_lib.lib().dmlp_radius_components(_p(X), N, X.shape[1], r2, _p(comp),
+                                                     _p(status), _stream()), "radius components")
+        if int(status.item()):
+            raise RuntimeError("radius components: a union-find walk overran its step bound")
+    return comp
+
+
+def exact_nearest_gpu(X, Qx, qidx):
+    """The nearest row of X (float64 [N, A] on a GPU) under (dist asc, id desc) for the rows qidx
+    (int32 tensor, any order) of Qx (float64 [Q, A] there): dmlp_exact_topk at k = 1 on the raw
+    device rows — no DeviceDataset, no screen.  Returns (dist float64 [Q], ids int32 [Q]) there,
+    (+inf, -1) for the rows that are not listed and, with N = 0, for all.  knn_cpu at k = 1 is its
+    CPU counterpart.  Asynchronous on the current stream."""
+    torch = _torch()
+    X, Qx = _device_rows(X), _device_rows(Qx, "Qx")
+    if Qx.shape[1] != X.shape[1] or Qx.device != X.device:
+        raise ValueError("Qx must have X's attribute count and device")
+    Q = Qx.shape[0]
+    if not torch.is_tensor(qidx) or qidx.dtype != torch.int32 or qidx.dim() != 1 or \
+            qidx.device != X.device:
+        raise ValueError("qidx must be an int32 [nb] tensor on X's device")
+    qidx = qidx.contiguous()
+    d = torch.full((Q,), float("inf"), dtype=torch.float64, device=X.device)
+    i = torch.full((Q,), -1, dtype=torch.int32, device=X.device)
+    if len(qidx) and X.shape[0]:
+        qk = torch.ones(Q, dtype=torch.int32, device=X.device)
+        _lib.check(_lib.lib().dmlp_exact_topk(_p(X), X.shape[0], X.shape[1], _p(Qx), _p(qidx),
+                                              _p(qk), len(qidx), 1, _p(d), _p(i), 1, _stream()),
+                   "exact nearest")
+    return d, i
 
 
 # ---------------------------------------------------------------- report text on the GPU
