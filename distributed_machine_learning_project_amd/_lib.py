@@ -82,6 +82,8 @@ _SIGS = {
                                   i32, i32, i32, vp, vp, vp, vp]),
     "dmlp_refine_groups": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
     "dmlp_refine_groups2": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "dmlp_refine_groups_exact": (i32, [i32, vp, vp, vp, i32, i64, vp, i32, vp, i64, vp, vp, i32, vp,
+                                       vp, i32, vp, vp, vp]),
     "dmlp_x1_seed": (i32, [vp, vp, i32, i32, vp, vp]),
     "dmlp_arena_reserve": (i32, [i64, i64]),
     "dmlp_knn_local": (i32, [vp, i64, i32, vp, i64, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]),

@@ -270,7 +270,10 @@ int dmlp_refine(int cap, const int* cand_ids, const int* cand_cnt, int S, const 
                 int* out_label, uint64_t* out_cs, int* status, int* ovf_count, void* stream);
 // Same for the single-term screen's group output: members of each group whose single-term score
 // (recomputed from xfrag / xinit / qhi, KT in {1,2,4,8}) reaches the (query, slice) threshold cand_h get
-// exact distances.  status = 1 also when the survivors exceed 256 (pathological ties).
+// exact distances.  status = 1 also when the survivors exceed the kernel's member slots
+// (pathological ties): 128 for dmlp_refine_groups, dmlp_refine_groups2(collect = 0) and
+// dmlp_refine_groups_rm off the pair path, 64 on the pair path (dmlp_refine_pair_path), 512 for
+// dmlp_refine_groups2(collect = 1) and dmlp_refine_groups_exact.
 // qidx may be null: query p is row p (the all-queries pass).
 int dmlp_refine_groups(int cap, const int* cand_ids, const int* cand_cnt, const float* cand_h,
                        int S, const double* X, int A, const double* Qx, const void* xfrag,
@@ -289,7 +292,8 @@ int dmlp_refine_groups2(int cap, const int* cand_ids, const int* cand_cnt, const
                         int* out_label, uint64_t* out_cs, int* status, int* ovf_count,
                         int collect, void* stream);
 // dmlp_refine_groups with the image also point-major (xrow, from dmlp_x1_rowmajor; nullptr: none)
-// and kmax = the largest k of the list (the two-queries-per-wave kernel serves kmax <= 32 only)
+// and kmax = the largest k of the list (the two-queries-per-wave kernel serves kmax <= 32 only).
+// ovf_count may be null on either path, as for dmlp_refine.
 int dmlp_refine_groups_rm(int cap, const int* cand_ids, const int* cand_cnt, const float* cand_h,
                           int S, const double* X, int A, const double* Qx, const void* xfrag,
                           const void* xrow, const float* xinit, const void* qhi, int KT, int hl,

@@ -1166,7 +1166,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KT == 1 ? D
   if (act && n < 0) {
     if (hl == 0) {
       status[q] = 1;
-      atomicAdd(ovf_count, 1);
+      if (ovf_count) atomicAdd(ovf_count, 1);
     }
     act = false;
   } else if (act && hl == 0) {
@@ -1259,7 +1259,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KT == 1 ? D
   if (act && nm > PM) {  // pathological ties: hand the query back
     if (hl == 0) {
       status[q] = 1;
-      atomicAdd(ovf_count, 1);
+      if (ovf_count) atomicAdd(ovf_count, 1);
     }
     act = false;
   }

@@ -1,0 +1,264 @@
+"""The refine kernels (csrc/refine.hip) against hand-built candidate lists, through the C ABI.
+
+tests/test_screen_contract.py and tests/test_exact_contract.py feed the refines the lists the real
+screens happen to write, so which branch of a refine runs is an accident of the screen.  Here the
+lists come from tests/helpers/refine_contract.py (pinned by tests/test_refine_contract_model.py):
+every family of cases sits on a boundary of the rule, and the reference says for every listed query
+the status, every slot of the list, the label and the checksum.  Outputs go into guarded buffers
+pre-filled with sentinels, *ovf_count starts at 5; every slot is compared with the reference bit
+for bit or must still hold its sentinel.
+
+Branches of refine.hip by family:
+  A  member slots: 64 (k_refine_pair), 128 (k_refine<2, KT>), 512 (k_refine<8, KT, true> collect
+     and exact) at capacity - 1, capacity and capacity + 1, the last group cut by n_points
+  B  the rank select's tie rule and summation order, the M > 64 && k <= 64 pre-filter, all members
+     at one distance, real rows at +inf before the padding
+  C  the member filter sc >= hq and the entry filter e >= kh at S = 1
+  D  the two-pass key histogram (S in {2, 4, 7, 256}, empty and short slices, duplicated k-th
+     key, M == k, M < k), the largest eps over the slices, the collect seed
+  E  nq around 4 / 8 queries per workgroup, qidx null / subset, k_q from 0 to kmax, overflowed
+     slices beside good ones, null labels, label spaces with and without a range
+  F  k_refine_pair's row loads: int4 (int32 rows), double2, scalar, a partial last chunk, KT 1 / 2
+  G  k_refine<4, 0> / <8, 0> on plain ids: rank select, pre-filter, RunTopK with re-sorts
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from distributed_machine_learning_project_amd import _lib
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import refine_contract as RF  # noqa: E402
+import result_contract as RC  # noqa: E402
+import test_screen_contract as TSC  # noqa: E402  (Ops: the operands of a reference on the device)
+
+pytestmark = pytest.mark.gpu
+
+OVF0 = 5     # *ovf_count before the call: the kernels add to it
+ENV_PATH = "DMLP_REFINE_PAIR" in os.environ or "DMLP_X1_SUB16_KMAX" in os.environ
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    _lib.lib()
+    return torch
+
+
+_p, _stream = TSC._p, TSC._stream
+_OPS = {}
+
+
+class PlainOps:
+    """fp64 rows only (dmlp_refine, dmlp_refine_groups_exact)"""
+
+    def __init__(self, torch, pr):
+        self.torch, self.L = torch, _lib.lib()
+        self.dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        self.X, self.Qx = self.dev(pr.X), self.dev(pr.Qx)
+
+
+def ops_of(torch, pr):
+    if pr.key not in _OPS:
+        if pr.ref is None:
+            _OPS[pr.key] = PlainOps(torch, pr)
+        else:
+            _OPS[pr.key] = TSC.Ops(torch, pr.ref, np.zeros(pr.N, np.int32))
+            if pr.hl == 2:   # eps from the words the device prep wrote: inside the builder's margin
+                assert (pr.ref.eps <= pr.eps * np.float32(1.0 + (RF.MARGIN - 1.0) / 2)).all()
+    return _OPS[pr.key]
+
+
+class Outputs:
+    def __init__(self, torch, Q, ks):
+        g = lambda shape, dt, **kw: RC.guarded(torch, shape, dt, **kw)
+        self.d, self.i = g((Q, ks), torch.float64), g((Q, ks), torch.int32)
+        self.lab, self.cs = g(Q, torch.int32), g(Q, torch.int64)
+        self.status, self.ovf = g(Q, torch.int32), g(1, torch.int32, fill=OVF0)
+        self.all = {"dist": self.d, "ids": self.i, "label": self.lab, "checksum": self.cs,
+                    "status": self.status, "ovf_count": self.ovf}
+
+
+def launch(torch, case, out, S=None, null_ovf=False):
+    """The case through its entry point; returns (return code, member slots of the kernel)."""
+    pr, v = case.prob, case.v
+    ops = ops_of(torch, pr)
+    L, dev = ops.L, ops.dev
+    S = case.S if S is None else S
+    ids, cnt, h = dev(case.ids.reshape(-1)), dev(case.cnt.reshape(-1)), dev(case.h.reshape(-1))
+    qk = dev(case.k)
+    qidx = None if case.qidx is None else dev(case.qidx.astype(np.int32))
+    labels, lo, hi = case.label_space()
+    dlab = None if labels is None else dev(labels)
+    lab_args = (_p(dlab), lo, hi, out.lab.ptr() if case.labels else None,
+                out.cs.ptr() if case.labels else None)
+    ovf = None if null_ovf else out.ovf.ptr()
+    tail = (_p(qidx), _p(qk), case.nq, out.d.ptr(), out.i.ptr(), case.kstride)
+    st = _stream(torch)
+    keep = (ids, cnt, h, qk, qidx, dlab)    # alive until the synchronize below
+    capacity = v.capacity
+    if v.entry == "refine":
+        rc = L.dmlp_refine(case.cap, _p(ids), _p(cnt), S, _p(ops.X), pr.A, _p(ops.Qx), *tail,
+                           *lab_args, out.status.ptr(), ovf, st)
+    elif v.entry == "exact":
+        rc = L.dmlp_refine_groups_exact(case.cap, _p(ids), _p(cnt), _p(h), S, case.tps, _p(ops.X),
+                                        pr.A, _p(ops.Qx), pr.N, *tail, out.status.ptr(), ovf, st)
+    else:
+        head = (case.cap, _p(ids), _p(cnt), _p(h), S, _p(ops.X), pr.A, _p(ops.Qx), _p(ops.xfrag))
+        mid = (_p(ops.xinit), _p(ops.qhi), pr.KT, pr.hl, pr.N)
+        if v.entry == "rm":
+            pair = L.dmlp_refine_pair_path(S, pr.hl, pr.KT, int(bool(case.labels)), case.cap,
+                                           case.kmax)
+            if not ENV_PATH:
+                assert pair == int(case.variant == "pair"), f"{case.name}: the other kernel ran"
+            capacity = RF.PAIR_MEMBERS if pair else RF.GROUP_MEMBERS
+            Xi, Qi = TSC.rows_i32(ops) if case.i32 else (None, None)
+            keep += (Xi, Qi)
+            rc = L.dmlp_refine_groups_rm(*head, _p(ops.xrow()) if pair else None, *mid, *tail,
+                                         *lab_args, out.status.ptr(), ovf, case.kmax, _p(Xi),
+                                         _p(Qi), st)
+        elif v.entry == "groups":
+            rc = L.dmlp_refine_groups(*head, *mid, *tail, *lab_args, out.status.ptr(), ovf, st)
+        else:
+            rc = L.dmlp_refine_groups2(*head, *mid, *tail, *lab_args, out.status.ptr(), ovf,
+                                       int(v.collect), st)
+    torch.cuda.synchronize()
+    del keep
+    return rc, capacity
+
+
+def check(case, out, ref, null_ovf=False):
+    """Every slot of every output against the reference or its sentinel."""
+    ctx = case.name
+    for name, g in out.all.items():
+        g.check_guards(f"{ctx} {name}")
+    Q, ks = case.prob.Q, case.kstride
+    rows = case.rows
+    listed = np.zeros(Q, bool)
+    listed[rows] = True
+    st = out.status.host()
+    np.testing.assert_array_equal(st[rows], ref.status, err_msg=f"{ctx}: status (survivors "
+                                  f"{ref.nsurv.tolist()})")
+    out.status.untouched(~listed, ctx + " status")
+    want_ovf = OVF0 + (0 if null_ovf else int(ref.status.sum()))
+    assert int(out.ovf.host()[0]) == want_ovf, f"{ctx}: *ovf_count"
+    d, i = out.d.host(), out.i.host()
+    keep = np.ones((Q, ks), bool)            # slots that must still hold the sentinel
+    voted = np.zeros(Q, bool)
+    for p, q in enumerate(rows):
+        kq = int(case.k[q])
+        if ref.status[p]:
+            keep[q, kq:] = False
+            assert (i[q, kq:] == -1).all() and np.isposinf(d[q, kq:]).all(), \
+                f"{ctx}: handed-back row {q}: slots [{kq}, {ks}) are not (+inf, -1)"
+            continue
+        keep[q] = False
+        voted[q] = True
+        np.testing.assert_array_equal(i[q], ref.i[p], err_msg=f"{ctx}: ids of row {q}")
+        np.testing.assert_array_equal(d[q], ref.d[p], err_msg=f"{ctx}: distances of row {q}")
+    out.d.untouched(keep, ctx + " dist")
+    out.i.untouched(keep, ctx + " ids")
+    if case.labels:
+        ok = ref.status == 0
+        np.testing.assert_array_equal(out.lab.host()[rows[ok]], ref.label[ok], err_msg=ctx)
+        np.testing.assert_array_equal(out.cs.host().view(np.uint64)[rows[ok]], ref.cs[ok],
+                                      err_msg=ctx)
+    else:
+        voted[:] = False
+    out.lab.untouched(~voted, ctx + " label")
+    out.cs.untouched(~voted, ctx + " checksum")
+
+
+def run_case(torch, case, null_ovf=False):
+    out = Outputs(torch, case.prob.Q, case.kstride)
+    rc, capacity = launch(torch, case, out, null_ovf=null_ovf)
+    assert rc == 0, f"{case.name}: return code {rc}"
+    ref = RF.refine_ref(case, capacity=capacity)
+    check(case, out, ref, null_ovf)
+    return ref
+
+
+def run_family(torch, cases):
+    failed = []
+    for case in cases:
+        try:
+            run_case(torch, case)
+        except AssertionError as e:
+            failed.append(f"{case.name}: {str(e).strip()[:600]}")
+    assert not failed, f"{len(failed)} of {len(cases)} cases:\n" + "\n".join(failed)
+
+
+def family(f):
+    return [c for c in RF.cases().values() if c.family == f]
+
+
+def test_capacity(torch_cuda):
+    """A: survivors at the member slots are all ranked, one more hands the query back, a last
+    group cut by n_points counts its real rows only."""
+    run_family(torch_cuda, family("A"))
+
+
+def test_order(torch_cuda):
+    """B: ties by descending id, the left-to-right sum on near-tied rows, true neighbours past
+    candidate position 64, all members at one distance, real rows at +inf before the padding."""
+    run_family(torch_cuda, family("B"))
+
+
+def test_threshold_decides(torch_cuda):
+    """C: fewer than k survive (the tail is padding a missing filter would fill), the survivors
+    sit at the member slots and one past them with many more members listed, a dead entry."""
+    run_family(torch_cuda, family("C"))
+
+
+def test_threshold_decides_bf16(torch_cuda):
+    """C on the device-rendered bf16 image (hl = 2), one case per k_refine group family."""
+    run_family(torch_cuda, RF.family_c(hl=2))
+
+
+def test_global_threshold(torch_cuda):
+    """D: the k-th largest key over the slices, minus twice the largest eps."""
+    run_family(torch_cuda, family("D"))
+
+
+@pytest.mark.parametrize("S", [0, 257])
+def test_slice_count_outside_the_range(torch_cuda, S):
+    """S = 256 is the limit (family D runs it): S = 0 and S = 257 return -1 before any launch and
+    write nothing."""
+    c = RF.cases()
+    for name in ("D-groups-S4", "D-groups2-S4", "D-collect-S4", "D-exact-S4", "G-refine-cap128-S4-A9"):
+        case = c[name]
+        out = Outputs(torch_cuda, case.prob.Q, case.kstride)
+        rc, _ = launch(torch_cuda, case, out, S=S)
+        assert rc == -1, f"{name}: S = {S} returned {rc}"
+        for what, g in out.all.items():
+            g.check_guards(f"{name} {what}")
+            g.untouched(np.ones(tuple(g.t.shape), bool), f"{name} S={S} {what}")
+
+
+def test_geometry(torch_cuda):
+    """E: query counts around a workgroup, listed subsets, every k_q, null labels."""
+    run_family(torch_cuda, family("E"))
+
+
+def test_pair_row_forms(torch_cuda):
+    """F: fp64 and lossless int32 rows of the pair kernel at every A class."""
+    run_family(torch_cuda, family("F"))
+
+
+def test_plain_id_lists(torch_cuda):
+    """G: dmlp_refine at cap 128, 256 and 512."""
+    run_family(torch_cuda, family("G"))
+
+
+def test_pair_null_ovf_count(torch_cuda):
+    """dmlp_refine_groups_rm with a null ovf_count on the pair path: a query past the member
+    slots and an overflowed slice are handed back (status 1, padding) and nothing is counted."""
+    c = RF.cases()
+    for name in (f"A-pair-A32-N{RF.N_ONE}", "E-pair-A32-nq9", "E-pair-A40-nq8"):
+        ref = run_case(torch_cuda, c[name], null_ovf=True)
+        assert ref.status.sum() >= 1
+    assert (RF.refine_ref(c["E-pair-A32-nq9"]).nsurv == -1).any()
