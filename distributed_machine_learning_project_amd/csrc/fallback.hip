@@ -5,7 +5,8 @@
 // distance: stability keeps equal distances in descending id, i.e. exactly the reference's
 // (dist asc, id desc) order without a 96-bit key.  The first k of each
 // row are copied out.  Rare path; the workspace comes from the caller (no allocation here, so
-// the call can be captured in a graph).
+// the call can be captured in a graph).  dmlp_exact_rows (k_exact_rows) writes the same rows in
+// ascending id order for a caller that selects from them itself.
 #include <hipcub/hipcub.hpp>
 
 #include "dmlp.h"
@@ -275,6 +276,61 @@ size_t sort_temp_bytes(int nb, int64_t N) {
 
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// 64 queries x 64 points per 256-thread block; each thread a 4x4 micro-tile; attributes staged
+// through LDS in chunks of 16 and accumulated strictly in attribute order.
+__global__ __launch_bounds__(256) void k_exact_rows(const double* __restrict__ X, int64_t N, int A,
+                                                    const double* __restrict__ Qx,
+                                                    const int* __restrict__ qidx, int nq,
+                                                    double* __restrict__ D, int64_t ldd) {
+  constexpr int AC = 16;
+  __shared__ double Qs[64][AC + 1];
+  __shared__ double Xs[64][AC + 1];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int64_t pt0 = (int64_t)blockIdx.x * 64;
+  const int qt0 = blockIdx.y * 64;
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+  for (int a0 = 0; a0 < A; a0 += AC) {
+    const int ac = A - a0 < AC ? A - a0 : AC;
+    for (int e = tid; e < 64 * AC; e += 256) {
+      const int r = e / AC, a = e % AC;
+      const int qi = qt0 + r;
+      Qs[r][a] = (qi < nq && a < ac) ? Qx[(int64_t)qidx[qi] * A + a0 + a] : 0.0;
+      const int64_t pi = pt0 + r;
+      Xs[r][a] = (pi < N && a < ac) ? X[pi * A + a0 + a] : 0.0;
+    }
+    __syncthreads();
+    for (int a = 0; a < ac; ++a) {
+      double qv[4], xv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) qv[i] = Qs[ty + 16 * i][a];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xv[j] = Xs[tx + 16 * j][a];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const double dd = __dsub_rn(qv[i], xv[j]);
+          acc[i][j] = __dadd_rn(acc[i][j], __dmul_rn(dd, dd));
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int qi = qt0 + ty + 16 * i;
+    if (qi >= nq) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t pi = pt0 + tx + 16 * j;
+      if (pi < N) D[(int64_t)qi * ldd + pi] = acc[i][j];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int dmlp_fallback_select_kmax(void) { return KSEL; }
@@ -341,6 +397,16 @@ extern "C" int dmlp_fallback_topk(const double* X, int64_t N, int A, const doubl
   const int maxk_blocks = 64;
   hipLaunchKernelGGL(k_take_k, dim3(maxk_blocks, nb), dim3(256), 0, st, D1, V1, N, qidx, qk, nb,
                      out_d, out_i, kstride);
+  DMLP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dmlp_exact_rows(const double* X, int64_t N, int A, const double* Qx,
+                               const int* qidx, int nq, double* D, int64_t ldd, void* stream) {
+  if (nq <= 0 || N <= 0) return 0;
+  const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((nq + 63) / 64));
+  hipLaunchKernelGGL(k_exact_rows, grid, dim3(256), 0, (hipStream_t)stream, X, N, A, Qx, qidx,
+                     nq, D, ldd);
   DMLP_LAUNCH_CHECK();
   return 0;
 }

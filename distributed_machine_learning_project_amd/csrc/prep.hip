@@ -10,6 +10,9 @@
 //   attributes kt*32 + (l>>4)*8 + j, j = 0..7  (mfma_f32_16x16x32_bf16 A map).
 //   hl = 0: hi = bf16(x - mu), hl = 1: lo = bf16((x - mu) - hi).
 //   xinit[t*64 + r] = -(|x-mu|^2)/2 in fp32 (the MFMA C-init; -inf for padding rows).
+//
+// k_x1_rowmajor (end of file) copies the host-rendered fp16 image of that layout point-major for
+// the pair refine's member loads.
 #include "dmlp.h"
 #include "dmlp_device.h"
 #include <float.h>
@@ -627,3 +630,29 @@ extern "C" int dmlp_render_rows(int KT, int A, const int* src32, const double* s
   return 0;
 }
 
+// The host-rendered fp16 image (tile layout of the screen's MFMA A operand: point p's 8-element
+// chunk f at u32x4 index tile * 256 KT + ((p & 63) >> 4) KT 64 + (f >> 2) 64 + 16 (f & 3) +
+// (p & 15)) copied point-major, xrow[p][f]: the pair refine's member loads then read one 64 KT
+// byte run per member instead of 4 KT separate lines
+__global__ __launch_bounds__(256) void k_x1_rowmajor(const u32x4* __restrict__ xfrag,
+                                                     int64_t n_items, int KT,
+                                                     u32x4* __restrict__ xrow) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // = p * 4 KT + f
+  if (i >= n_items) return;
+  const int nf = 4 * KT;
+  const int64_t pt = i / nf;
+  const int f = (int)(i - pt * nf), kt = f >> 2, kq = f & 3;
+  xrow[i] = xfrag[(pt >> 6) * (4 * KT * 64) + ((((pt & 63) >> 4) * KT + kt) * 64) + 16 * kq +
+                  (pt & 15)];
+}
+
+extern "C" int dmlp_x1_rowmajor(const void* xfrag, int64_t n_tiles, int KT, void* xrow,
+                                void* stream) {
+  if (n_tiles <= 0) return 0;
+  if (KT < 1 || KT > 8) return -1;
+  const int64_t n = n_tiles * 64 * 4 * KT;
+  hipLaunchKernelGGL(k_x1_rowmajor, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const u32x4*)xfrag, n, KT, (u32x4*)xrow);
+  DMLP_LAUNCH_CHECK();
+  return 0;
+}

@@ -1,7 +1,7 @@
 // screen_x1.hip — single-term MFMA screen (fp16 host-rendered operands, bf16 device image) with lane-parallel batched threshold compaction.
 //
 // Same contract as screen_stream.hip (candidate ids per (query, slice), exact fp64 re-rank in
-// refine.hip), different balance:
+// refine.hip / refine_pair.hip), different balance:
 //
 //  * ONE bf16 product per attribute (hi(q') * hi(x')), not the 3-term split: a third of the MFMA
 //    work and half the fragment bytes.  The price is a wider error bound,

@@ -1,5 +1,5 @@
 """References for the operand-prep, int32 row transfer and report kernels (prep.hip, the
-formatter of refine.hip), NumPy and Python integers only — nothing here calls libdmlp.
+formatter of report.hip), NumPy and Python integers only — nothing here calls libdmlp.
 tests/test_operand_contract_model.py pins them against torch's bfloat16 cast and the CPU
 implementations; the GPU contract tests compare kernels with them bit for bit.
 
@@ -106,7 +106,7 @@ def hi_image(rows16, KT):
 
 def rowmajor(chunks, KT):
     """chunks [n_tiles * 64 * 4 KT, ...] of the tile image -> point-major [p * 4 KT + f]
-    (refine.hip k_x1_rowmajor: chunk f of point p sits at tile 256 KT + ((p & 63) >> 4) KT 64 +
+    (prep.hip k_x1_rowmajor: chunk f of point p sits at tile 256 KT + ((p & 63) >> 4) KT 64 +
     (f >> 2) 64 + 16 (f & 3) + (p & 15))."""
     nf = 4 * KT
     n = chunks.shape[0]

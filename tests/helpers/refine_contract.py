@@ -1,11 +1,11 @@
-"""Hand-built candidate lists for the refine kernels (csrc/refine.hip) and the float64 reference of
-what a refine must write for them.  NumPy and the CPU side of libdmlp only: no GPU.
+"""Hand-built candidate lists for the refine kernels (csrc/refine.hip, csrc/refine_pair.hip) and the
+float64 reference of what a refine must write for them.  NumPy and the CPU side of libdmlp only: no GPU.
 
 The screens list generously, so on their lists most of the refine's rule cannot be seen: a
 dropped non-neighbour changes nothing.  Here the lists are written by hand — which groups, in
 which order, how many, which threshold — so that every branch of the rule decides the answer.
 
-The rule (refine.hip, k_refine / k_refine_pair), per listed query p of row q:
+The rule (refine.hip k_refine / refine_pair.hip k_refine_pair), per listed query p of row q:
   overflow   a slice count of -1 -> status 1
   threshold  one slice, not collect: hq = cand_h[p][0][0]; collect: hq starts at slice 0's seed;
              S > 1 or collect, and M >= k >= 1 (M: listed entries): hq = max(hq, decode16(k-th

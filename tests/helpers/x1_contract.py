@@ -87,7 +87,7 @@ def slice_rows(n_tiles: int, S: int, s: int, N: int):
 
 def group_rows(gi, grows: int):
     """Slice-relative rows of the members of group entries gi -> [len(gi), grows] (group_row in
-    refine.hip): 4 consecutive rows, or the pair epilogue's rows 4 kg + i of steps 2 p, 2 p + 1."""
+    refine_common.h): 4 consecutive rows, or the pair epilogue's rows 4 kg + i of steps 2 p, 2 p + 1."""
     gi = np.asarray(gi, np.int64).reshape(-1, 1)
     i = np.arange(grows, dtype=np.int64).reshape(1, -1)
     if grows == 8:

@@ -1,5 +1,5 @@
-"""Kernel-level contract of the operand prep and the int32 row transfer (prep.hip) and of the
-point-major copy (refine.hip k_x1_rowmajor), through the C ABI.
+"""Kernel-level contract of the operand prep, the int32 row transfer and the point-major copy
+(prep.hip; the copy: k_x1_rowmajor), through the C ABI.
 
 End-to-end runs reach these kernels on uniform six-decimal data only, where the later stages
 repair or hide a wrong bit.  Here every entry point is called directly into outputs with

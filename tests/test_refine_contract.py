@@ -1,4 +1,4 @@
-"""The refine kernels (csrc/refine.hip) against hand-built candidate lists, through the C ABI.
+"""The refine kernels (csrc/refine.hip, csrc/refine_pair.hip) against hand-built candidate lists, through the C ABI.
 
 tests/test_screen_contract.py and tests/test_exact_contract.py feed the refines the lists the real
 screens happen to write, so which branch of a refine runs is an accident of the screen.  Here the
@@ -8,7 +8,7 @@ the status, every slot of the list, the label and the checksum.  Outputs go into
 pre-filled with sentinels, *ovf_count starts at 5; every slot is compared with the reference bit
 for bit or must still hold its sentinel.
 
-Branches of refine.hip by family:
+Branches of refine.hip (k_refine) and refine_pair.hip (k_refine_pair) by family:
   A  member slots: 64 (k_refine_pair), 128 (k_refine<2, KT>), 512 (k_refine<8, KT, true> collect
      and exact) at capacity - 1, capacity and capacity + 1, the last group cut by n_points
   B  the rank select's tie rule and summation order, the M > 64 && k <= 64 pre-filter, all members

@@ -1,5 +1,5 @@
-"""Kernel-level contract of the report formatter (refine.hip k_fmt_len / k_fmt_scan_blocks /
-k_fmt_write) and of the two small fill kernels, through the C ABI.
+"""Kernel-level contract of the report formatter (report.hip k_fmt_len / k_fmt_scan_blocks /
+k_fmt_write) and of the two small fill kernels (merge.hip), through the C ABI.
 
 The text goes into exactly dmlp_format_bound(nq) bytes and the scratch into exactly
 dmlp_format_scratch(nq) int64, both between sentinel bands (tests/helpers/result_contract.py:

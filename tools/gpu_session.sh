@@ -378,13 +378,6 @@ for task in "$@"; do
       AB_PROF=0 AB_ROUNDS=4 AB_STEPS=200 step prio_ab 900 bash tools/kernel_ab.sh \
           p0:DMLP_SIDE_PRIORITY=0 p1:DMLP_SIDE_PRIORITY=1
       grep -Ho '"ms_per_step": [0-9.]*' gpurun_out/ab/p*.log | tee "$OUT/prio_ab.txt" ;;
-    refabl)  # the pair refine's time with its exact-row gathers / member loads ablated
-             # (DMLP_REFINE_ABL 1 / 2 / 3: wrong results, timing only), native step driver
-      for AB in 0 1 2 3; do
-        DMLP_REFINE_ABL=$AB step refabl_$AB 120 rocprofv3 --kernel-trace --stats -d "$OUT/refabl_$AB" \
-            -o run --output-format csv -- tools/bin/step_driver --steps 20 --warmup 5
-        echo "abl=$AB: $(grep -h k_refine_pair "$OUT/refabl_$AB/run_kernel_stats.csv" | cut -d, -f2-4)"
-      done ;;
     h2dbw)  # H2D bandwidth from page-locked memory over 1 / 2 / 4 concurrent streams
       step h2dbw 120 tools/bin/h2d_bw ;;
     pyck)  # the NoCU copies from a Python process, with / without torch initialised first
