@@ -80,6 +80,11 @@ _SIGS = {
     "dmlp_x1_rowmajor": (i32, [vp, i64, i32, vp, vp]),
     "dmlp_screen_x1_part": (i32, [i32, i32, i32, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, vp, vp,
                                   i32, i32, i32, vp, vp, vp, vp]),
+    # ... with the uniform k as a scalar (kuni, in front of nq)
+    "dmlp_screen_x1_part_k": (i32, [i32, i32, i32, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32,
+                                    vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "dmlp_screen_x1_early_k": (i32, [i32, i32, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, vp,
+                                     vp, i32, i32, vp, vp, vp, vp, vp]),
     "dmlp_refine_groups": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
     "dmlp_refine_groups2": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp]),
     "dmlp_refine_groups_exact": (i32, [i32, vp, vp, vp, i32, i64, vp, i32, vp, i64, vp, vp, i32, vp,

@@ -214,9 +214,10 @@ int dmlp_screen_x1_qw(int KT);
 int dmlp_screen_x1_cols(int KT, int kmax);
 int dmlp_screen_x1_cap(int kmax);  // (KT 1's; the image of KT fragments per step: _kt)
 int dmlp_screen_x1_cap_kt(int KT, int kmax);
-// rows per group entry of that screen's lists: 8 for kmax <= 16 (hit test and append once per two
-// MFMA steps on the 8-row max: rows 4 kg .. 4 kg + 3 of steps 2p and 2p + 1, entry index 4 p + kg),
-// else 4 (consecutive rows, entry index = row / 4); the refines expand each entry to its rows
+// rows per group entry of that screen's lists: 8 for kmax <= 32 at every KT and for kmax <= 64 at
+// KT 1 (hit test and append once per two MFMA steps on the 8-row max: rows 4 kg .. 4 kg + 3 of
+// steps 2p and 2p + 1, entry index 4 p + kg), else 4 (consecutive rows, entry index = row / 4;
+// the COLLECT pass always); the refines expand each entry to its rows
 int dmlp_screen_x1_group_rows(int kmax);
 int dmlp_screen_x1_group_rows_kt(int KT, int kmax);
 int dmlp_screen_x1_waves_per_cu(int kmax);
@@ -235,7 +236,13 @@ int dmlp_screen_x1(int KT, int hl, int A, const void* xfrag, const float* xinit,
                    const int* qk, int nq, int kmax, const unsigned* xnmax_bits,
                    const unsigned* bad, int S, int* cand_ids, int* cand_cnt, float* cand_h,
                    void* stream);
-// ... slices [s_first, s_first + S_l) of it only (the candidate lists laid out for all S)
+// ... slices [s_first, s_first + S_l) of it only (the candidate lists laid out for all S).
+// Returns 0 (also for nq <= 0 or S_l <= 0: nothing to do), or before any launch, in this order:
+// -1 for kuni > kmax, S < 1, s_first < 0, s_first + S_l > S, n_tiles outside [0, INT_MAX / 64] or
+// n_points > 64 n_tiles; -4 for a slice of more than 4096 tiles (the 16-bit group index);
+// -3 for kmax > 64, KT outside {1, 2, 4, 8} or A > 32 KT; -1 for hl outside {1, 2}.
+// dmlp_screen_x1_collect: the same -1 / -4 / -3; dmlp_screen_x1_early: -1 also for n_tiles
+// outside [1, 4096], a null rdy or rdy_tiles * rdy_n < n_tiles.  A rejected call writes nothing.
 int dmlp_screen_x1_part(int KT, int hl, int A, const void* xfrag, const float* xinit,
                         int64_t n_tiles, int64_t n_points, const void* qhi, const float* qn,
                         const int* qidx, const int* qk, int nq, int kmax,

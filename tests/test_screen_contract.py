@@ -85,14 +85,21 @@ class Ops:
     """The operands of one reference on the device: host-rendered (hl = 1) or written by
     dmlp_prep_data / dmlp_prep_queries (hl = 2, with qlo for the 3-term screens)."""
 
-    def __init__(self, torch, ref, labels, label_range=(0, 10)):
+    def __init__(self, torch, ref, labels, label_range=(0, 10), qidx=None, qk=None):
+        """qidx: the query list (distinct rows, any order; None: every row in order), rows on the
+        host; qk: a device k array in place of ref.k's (indexed by row, like it)."""
         self.torch, self.ref = torch, ref
         L = self.L = _lib.lib()
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
         self.dev = dev
         self.X, self.Qx = dev(ref.X), dev(ref.Qx)
-        self.qk = dev(ref.k.astype(np.int32))
-        self.qidx = dev(np.arange(ref.Q, dtype=np.int32))
+        self.qk = dev(ref.k.astype(np.int32)) if qk is None else qk
+        self.rows = np.arange(ref.Q, dtype=np.int32) if qidx is None \
+            else np.ascontiguousarray(qidx, np.int32)
+        assert len(np.unique(self.rows)) == len(self.rows) and self.rows.min() >= 0 \
+            and self.rows.max() < ref.Q
+        self.nq = len(self.rows)
+        self.qidx = dev(self.rows)
         self.set_labels(labels, label_range)
         self.words = torch.zeros(2, dtype=torch.int32, device="cuda")  # [0] max norm, [1] bad
         N, A, KT, nt, Q = ref.N, ref.A, ref.KT, ref.n_tiles, ref.Q
@@ -148,34 +155,64 @@ class Ops:
 
 
 class Lists:
-    def __init__(self, torch, nq, S, cap):
-        self.nq, self.S, self.cap = nq, S, cap
-        self.ids = torch.zeros(nq * S * cap, dtype=torch.int32, device="cuda")
-        self.cnt = torch.full((nq * S,), -7, dtype=torch.int32, device="cuda")  # -7: never written
-        self.h = torch.full((nq * S * 2,), float("nan"), dtype=torch.float32, device="cuda")
+    """The lists of nq positions and, behind them, a sentinel band of `band` more positions that
+    no kernel may write (counts -7, ids -7, h NaN)."""
+
+    def __init__(self, torch, nq, S, cap, band=3):
+        self.nq, self.S, self.cap, self.band = nq, S, cap, band
+        n = nq + band
+        self.ids = torch.zeros(n * S * cap, dtype=torch.int32, device="cuda")
+        self.ids[nq * S * cap:] = -7
+        self.cnt = torch.full((n * S,), -7, dtype=torch.int32, device="cuda")  # -7: never written
+        self.h = torch.full((n * S * 2,), float("nan"), dtype=torch.float32, device="cuda")
 
     def host(self):
-        return (self.ids.cpu().numpy().reshape(self.nq, self.S, self.cap),
-                self.cnt.cpu().numpy().reshape(self.nq, self.S),
-                self.h.cpu().numpy().reshape(self.nq, self.S, 2))
+        n = self.nq * self.S
+        return (self.ids.cpu().numpy()[:n * self.cap].reshape(self.nq, self.S, self.cap),
+                self.cnt.cpu().numpy()[:n].reshape(self.nq, self.S),
+                self.h.cpu().numpy()[:2 * n].reshape(self.nq, self.S, 2))
+
+    def check_band(self, ctx=""):
+        """the positions past nq still hold their sentinels"""
+        n = self.nq * self.S
+        assert (self.cnt.cpu().numpy()[n:] == -7).all(), f"{ctx}: a count past nq was written"
+        assert (self.ids.cpu().numpy()[n * self.cap:] == -7).all(), f"{ctx}: ids past nq written"
+        assert np.isnan(self.h.cpu().numpy()[2 * n:]).all(), f"{ctx}: cand_h past nq written"
+
+    def untouched(self, ctx=""):
+        """nothing at all was written: every count -7, every h NaN, the ids as preset"""
+        self.check_band(ctx)
+        ids, cnt, h = self.host()
+        assert (cnt == -7).all() and np.isnan(h).all() and (ids == 0).all(), \
+            f"{ctx}: a rejected call wrote into the lists"
 
 
-def run_x1(ops, kmax, S, parts=None, qk=None):
-    """dmlp_screen_x1, or dmlp_screen_x1_part over the (s_first, S_l) of `parts`."""
+NULL = object()   # qk=NULL: a null k pointer (the scalar-k entry points must not read it)
+
+
+def run_x1(ops, kmax, S, parts=None, qk=None, kuni=None):
+    """dmlp_screen_x1, or dmlp_screen_x1_part over the (s_first, S_l) of `parts`; with kuni set,
+    dmlp_screen_x1_part_k with that scalar k (over `parts`, or over all S slices at once)."""
     torch, L, r = ops.torch, ops.L, ops.ref
     cap = L.dmlp_screen_x1_cap_kt(r.KT, kmax)
     assert S >= L.dmlp_screen_x1_min_slices(r.n_tiles)
-    ls = Lists(torch, r.Q, S, cap)
-    qk = ops.qk if qk is None else qk
-    common = (r.KT, r.hl, r.A, _p(ops.xfrag), _p(ops.xinit), r.n_tiles, r.N, _p(ops.qhi),
-              _p(ops.qn), _p(ops.qidx), _p(qk), r.Q, kmax, ops.xnmax, ops.bad, S)
+    ls = Lists(torch, ops.nq, S, cap)
+    qk = None if qk is NULL else ops.qk if qk is None else qk
+    head = (r.KT, r.hl, r.A, _p(ops.xfrag), _p(ops.xinit), r.n_tiles, r.N, _p(ops.qhi),
+            _p(ops.qn), _p(ops.qidx), _p(qk))
+    mid = (ops.nq, kmax, ops.xnmax, ops.bad, S)
     tail = (_p(ls.ids), _p(ls.cnt), _p(ls.h), _stream(torch))
-    if parts is None:
-        _lib.check(L.dmlp_screen_x1(*common, *tail), "screen_x1")
+    if kuni is not None:
+        for s_first, S_l in ([(0, S)] if parts is None else parts):
+            _lib.check(L.dmlp_screen_x1_part_k(*head, kuni, *mid, s_first, S_l, *tail),
+                       "screen_x1_part_k")
+    elif parts is None:
+        _lib.check(L.dmlp_screen_x1(*head, *mid, *tail), "screen_x1")
     else:
         for s_first, S_l in parts:
-            _lib.check(L.dmlp_screen_x1_part(*common, s_first, S_l, *tail), "screen_x1_part")
+            _lib.check(L.dmlp_screen_x1_part(*head, *mid, s_first, S_l, *tail), "screen_x1_part")
     torch.cuda.synchronize()
+    ls.check_band("screen_x1")
     return ls
 
 
@@ -194,45 +231,59 @@ def ready_words(ref, rdy_tiles):
     return bits
 
 
-def run_x1_early(ops, kmax, rdy_tiles):
+def run_x1_early(ops, kmax, rdy_tiles, qk=None, kuni=None):
+    """dmlp_screen_x1_early; with kuni set, dmlp_screen_x1_early_k with that scalar k."""
     torch, L, r = ops.torch, ops.L, ops.ref
     assert r.hl == 1
     cap = L.dmlp_screen_x1_cap_kt(r.KT, kmax)
-    ls = Lists(torch, r.Q, 1, cap)
+    ls = Lists(torch, ops.nq, 1, cap)
+    qk = None if qk is NULL else ops.qk if qk is None else qk
     bits = ready_words(r, rdy_tiles)
     # the slices' maxima fold to the image's max-norm word: I1 is taken against that
     assert bits.max() == r.xnmax_bits[0]
     rdy = torch.from_numpy(bits.view(np.int32)).cuda()   # preset: nothing can wait
     estats = torch.zeros(3, dtype=torch.int32, device="cuda")
-    _lib.check(L.dmlp_screen_x1_early(r.KT, r.A, _p(ops.xfrag), _p(ops.xinit), r.n_tiles, r.N,
-                                      _p(ops.qhi), _p(ops.qn), _p(ops.qidx), _p(ops.qk), r.Q, kmax,
-                                      ops.bad, _p(rdy), rdy_tiles, len(bits), _p(ls.ids),
-                                      _p(ls.cnt), _p(ls.h), _p(estats), _stream(torch)),
-               "screen_x1_early")
+    head = (r.KT, r.A, _p(ops.xfrag), _p(ops.xinit), r.n_tiles, r.N, _p(ops.qhi), _p(ops.qn),
+            _p(ops.qidx), _p(qk))
+    tail = (ops.nq, kmax, ops.bad, _p(rdy), rdy_tiles, len(bits), _p(ls.ids), _p(ls.cnt),
+            _p(ls.h), _p(estats), _stream(torch))
+    if kuni is not None:
+        _lib.check(L.dmlp_screen_x1_early_k(*head, kuni, *tail), "screen_x1_early_k")
+    else:
+        _lib.check(L.dmlp_screen_x1_early(*head, *tail), "screen_x1_early")
     torch.cuda.synchronize()
+    ls.check_band("screen_x1_early")
     return ls, estats.cpu().numpy()
 
 
 # ------------------------------------------------------------------ the invariants
-def check_lists(ref, ls, grows, k=None, ctx="", thresholds=True, max_ovf_frac=0.0):
+def check_lists(ref, ls, grows, k=None, ctx="", thresholds=True, max_ovf_frac=0.0, rows=None):
     """I1 - I5 on the lists of a single-term screen (thresholds=False: a COLLECT pass' lists, whose
-    cand_h holds the fixed seed: I1, I2 and the entry checks of I4 only)."""
+    cand_h holds the fixed seed: I1, I2 and the entry checks of I4 only).  rows: the query list —
+    list position p is judged against reference row rows[p] (None: position p is row p); k is
+    indexed by row, like ref.k."""
     ids, cnt, h = ls.host()
     S, cap = ls.S, ls.cap
     cape = cap - 4 if thresholds else cap     # 4 (SUB - 2) of 4 (SUB - 1); COLLECT: ccap
     k = ref.k if k is None else k
-    eps = ref.eps.astype(np.float64)
+    a_exact, nn_i, eps32 = ref.a_exact, ref.nn_i, ref.eps
+    if rows is not None:
+        rows = np.asarray(rows, np.int64)
+        a_exact, nn_i, eps32, k = a_exact[rows], nn_i[rows], eps32[rows], np.asarray(k)[rows]
+    nq = a_exact.shape[0]
+    assert cnt.shape == (nq, S), f"{ctx}: lists of {cnt.shape[0]} positions for {nq} queries"
+    eps = eps32.astype(np.float64)
     tps = X1.tiles_per_slice(ref.n_tiles, S)
     assert (cnt != -7).all(), f"{ctx}: a (query, slice) count was never written"
     n_ovf = 0
     for s in range(S):
-        np.testing.assert_allclose(h[:, s, 1], ref.eps, rtol=1e-5, err_msg=f"{ctx}: I1 slice {s}")
+        np.testing.assert_allclose(h[:, s, 1], eps32, rtol=1e-5, err_msg=f"{ctx}: I1 slice {s}")
         r0, r1 = X1.slice_rows(ref.n_tiles, S, s, ref.N)
         nts = max(0, min((s + 1) * tps, ref.n_tiles) - s * tps)
-        ae = ref.a_exact[:, r0:r1]
+        ae = a_exact[:, r0:r1]
         gmax = X1.group_max(ae, nts, grows)
         ng = gmax.shape[1]
-        for p in range(ref.Q):
+        for p in range(nq):
             where = f"{ctx}: query {p} slice {s}"
             c, kq = int(cnt[p, s]), int(k[p])
             real = np.nonzero(gmax[p] > -np.inf)[0]
@@ -248,7 +299,7 @@ def check_lists(ref, ls, grows, k=None, ctx="", thresholds=True, max_ovf_frac=0.
             assert (gi < ng).all(), f"{where}: I4 group index outside the slice"
             gm = gmax[p, gi]
             assert (gm > -np.inf).all(), f"{where}: I4 a group of padding rows is listed"
-            nn = ref.nn_i[p, :min(kq, ref.N)].astype(np.int64)
+            nn = nn_i[p, :min(kq, ref.N)].astype(np.int64)
             nn = nn[(nn >= r0) & (nn < r1)]
             lost = nn[~np.isin(X1.group_of_row(nn - s * tps * 64, grows), gi)]
             assert len(lost) == 0, f"{where}: I2 oracle neighbours {lost.tolist()} not listed"
@@ -264,7 +315,7 @@ def check_lists(ref, ls, grows, k=None, ctx="", thresholds=True, max_ovf_frac=0.
                     f"{where}: I3 h {hs!r} above t_s - eps = {t_s - eps[p]!r}"
             elif kq >= 1:
                 assert np.isin(real, gi).all(), f"{where}: I3 short slice, a real group is missing"
-    assert n_ovf <= max_ovf_frac * ref.Q * S, f"{ctx}: {n_ovf} overflowed (query, slice) pairs"
+    assert n_ovf <= max_ovf_frac * nq * S, f"{ctx}: {n_ovf} overflowed (query, slice) pairs"
 
 
 def grows_of(L, ref, kmax):
@@ -281,22 +332,31 @@ class Out:
         self.d = torch.full((Q, kstride), float("nan"), dtype=torch.float64, device="cuda")
         self.i = torch.full((Q, kstride), -9, dtype=torch.int32, device="cuda")
         self.lab = torch.full((Q,), -9, dtype=torch.int32, device="cuda")
-        self.cs = torch.zeros(Q, dtype=torch.int64, device="cuda")
+        self.cs = torch.full((Q,), -9, dtype=torch.int64, device="cuda")
         self.status = torch.full((Q,), -9, dtype=torch.int32, device="cuda")
         self.ovf = torch.zeros(1, dtype=torch.int32, device="cuda")
 
 
-def check_refined(ops, out, with_labels, ctx, handed_back=None):
+def check_refined(ops, out, with_labels, ctx, handed_back=None, rows=None):
     """status == 0 for every query (1 exactly for those of handed_back: a screen overflow), and
-    the lists equal the oracle bit for bit (ids, order, distances; label and checksum when voted)."""
+    the lists equal the oracle bit for bit (ids, order, distances; label and checksum when voted).
+    rows: the query list the refine was given (None: every row in order); handed_back is indexed
+    by list position, the outputs by row (the refines write out[q], q = qidx[p]), and the rows of
+    unlisted queries keep every sentinel."""
     ops.torch.cuda.synchronize()
     ref = ops.ref
+    rows = np.arange(ref.Q) if rows is None else np.asarray(rows, np.int64)
     st = out.status.cpu().numpy()
-    want = np.zeros(ref.Q, np.int32) if handed_back is None else handed_back.astype(np.int32)
+    want = np.full(ref.Q, -9, np.int32)
+    want[rows] = 0 if handed_back is None else np.asarray(handed_back).astype(np.int32)
     assert (st == want).all(), f"{ctx}: status {st.tolist()}"
-    assert int(out.ovf.cpu()[0]) == int(want.sum())
+    assert int(out.ovf.cpu()[0]) == int((want == 1).sum())
     done = np.nonzero(want == 0)[0]
     d, i = out.d.cpu().numpy(), out.i.cpu().numpy()
+    un = want == -9
+    assert np.isnan(d[un]).all() and (i[un] == -9).all(), f"{ctx}: a row of an unlisted query written"
+    assert (out.lab.cpu().numpy()[un] == -9).all() and (out.cs.cpu().numpy()[un] == -9).all(), \
+        f"{ctx}: label / checksum of an unlisted query written"
     for q in done:
         kq = min(int(ref.k[q]), ref.N)
         np.testing.assert_array_equal(i[q, :kq], ref.nn_i[q, :kq], err_msg=f"{ctx}: ids q={q}")
@@ -337,11 +397,12 @@ def refine_rm(ops, ls, kmax, with_labels, ctx, i32=False):
     _lib.check(L.dmlp_refine_groups_rm(
         ls.cap, _p(ls.ids), _p(ls.cnt), _p(ls.h), ls.S, _p(ops.X), r.A, _p(ops.Qx), _p(ops.xfrag),
         _p(ops.xrow()) if pair else None, _p(ops.xinit), _p(ops.qhi), r.KT, r.hl, r.N,
-        _p(ops.qidx), _p(ops.qk), r.Q, _p(out.d), _p(out.i), out.kstride,
+        _p(ops.qidx), _p(ops.qk), ops.nq, _p(out.d), _p(out.i), out.kstride,
         *_label_args(ops, out, with_labels), _p(out.status), _p(out.ovf), kmax, _p(Xi), _p(Qi),
         _stream(torch)), "refine_groups_rm")
     check_refined(ops, out, with_labels,
-                  f"{ctx} refine_groups_rm pair={pair} labels={with_labels} i32={i32}")
+                  f"{ctx} refine_groups_rm pair={pair} labels={with_labels} i32={i32}",
+                  rows=ops.rows)
     return pair
 
 
@@ -351,19 +412,19 @@ def refine_groups(ops, ls, kmax, ctx, collect=None):
     out = Out(torch, r.Q, max(kmax, 1))
     args = (ls.cap, _p(ls.ids), _p(ls.cnt), _p(ls.h), ls.S, _p(ops.X), r.A, _p(ops.Qx),
             _p(ops.xfrag), _p(ops.xinit), _p(ops.qhi), r.KT, r.hl, r.N, _p(ops.qidx), _p(ops.qk),
-            r.Q, _p(out.d), _p(out.i), out.kstride, *_label_args(ops, out, True), _p(out.status),
+            ops.nq, _p(out.d), _p(out.i), out.kstride, *_label_args(ops, out, True), _p(out.status),
             _p(out.ovf))
     if collect is None:
         _lib.check(L.dmlp_refine_groups(*args, _stream(torch)), "refine_groups")
     else:
         _lib.check(L.dmlp_refine_groups2(*args, collect, _stream(torch)), "refine_groups2")
-    check_refined(ops, out, True, f"{ctx} refine_groups collect={collect}")
+    check_refined(ops, out, True, f"{ctx} refine_groups collect={collect}", rows=ops.rows)
 
 
-def screen_and_refine(torch, adv_or_inp, ref, kmax, S, ctx, parts=None):
-    ops = Ops(torch, ref, adv_or_inp.labels)
+def screen_and_refine(torch, adv_or_inp, ref, kmax, S, ctx, parts=None, qidx=None):
+    ops = Ops(torch, ref, adv_or_inp.labels, qidx=qidx)
     ls = run_x1(ops, kmax, S, parts)
-    check_lists(ref, ls, grows_of(ops.L, ref, kmax), ctx=ctx)
+    check_lists(ref, ls, grows_of(ops.L, ref, kmax), ctx=ctx, rows=qidx)
     for with_labels in (True, False):
         refine_rm(ops, ls, kmax, with_labels, ctx)
     refine_groups(ops, ls, kmax, ctx)
@@ -428,6 +489,31 @@ def test_x1_early_preset(torch_cuda, kind, A):
 
 
 # ------------------------------------------------------------------ two-pass large k
+def run_x1_collect(ops, hseed, ccap, S):
+    """dmlp_screen_x1_collect at the seeds hseed (per list position)"""
+    torch, L, r = ops.torch, ops.L, ops.ref
+    ls = Lists(torch, ops.nq, S, ccap)
+    _lib.check(L.dmlp_screen_x1_collect(
+        r.KT, r.A, _p(ops.xfrag), _p(ops.xinit), r.n_tiles, r.N, _p(ops.qhi), _p(ops.qn),
+        _p(ops.qidx), _p(ops.qk), ops.nq, ops.xnmax, ops.bad, _p(hseed), ccap, S, _p(ls.ids),
+        _p(ls.cnt), _p(ls.h), _stream(torch)), "screen_x1_collect")
+    torch.cuda.synchronize()
+    ls.check_band("screen_x1_collect")
+    return ls
+
+
+def first_pass_seed(ops, S1):
+    """The two-pass form's first pass: k' = ceil(k / S1) per row over S1 slices, then dmlp_x1_seed
+    -> (the first pass' lists, k' by row, the seeds by list position)."""
+    torch, r = ops.torch, ops.ref
+    kp = ((np.maximum(r.k, 1) + S1 - 1) // S1).astype(np.int32)
+    first = run_x1(ops, int(kp.max()), S1, qk=torch.from_numpy(kp).cuda())
+    hseed = torch.full((ops.nq,), float("nan"), dtype=torch.float32, device="cuda")
+    _lib.check(ops.L.dmlp_x1_seed(_p(first.h), _p(first.cnt), S1, ops.nq, _p(hseed),
+                                  _stream(torch)), "x1_seed")
+    return first, kp, hseed
+
+
 @pytest.mark.parametrize("k", [33, 100, 256])
 @pytest.mark.parametrize("A", [32, 100])
 def test_x1_two_pass(torch_cuda, A, k):
@@ -449,13 +535,7 @@ def test_x1_two_pass(torch_cuda, A, k):
                "x1_seed")
 
     def collect(seed):
-        ls = Lists(torch, ref.Q, S2, ccap)
-        _lib.check(L.dmlp_screen_x1_collect(
-            ref.KT, ref.A, _p(ops.xfrag), _p(ops.xinit), ref.n_tiles, ref.N, _p(ops.qhi),
-            _p(ops.qn), _p(ops.qidx), _p(ops.qk), ref.Q, ops.xnmax, ops.bad, _p(seed), ccap, S2,
-            _p(ls.ids), _p(ls.cnt), _p(ls.h), _stream(torch)), "screen_x1_collect")
-        torch.cuda.synchronize()
-        return ls
+        return run_x1_collect(ops, seed, ccap, S2)
 
     ls = collect(hseed)
     hs = hseed.cpu().numpy().astype(np.float64)
@@ -477,35 +557,38 @@ def test_x1_two_pass(torch_cuda, A, k):
 
 
 # ------------------------------------------------------------------ 3-term screens: completeness
-def check_id_lists(ref, ids, cnt, S, ctx):
+def check_id_lists(ref, ids, cnt, S, ctx, rows=None):
     """Every oracle neighbour of a slice is in the slice's candidate list (global point ids, as
-    dmlp_refine reads them), or the count is -1."""
+    dmlp_refine reads them), or the count is -1.  rows: the query list (position p is row rows[p];
+    None: row p)."""
     tps = X1.tiles_per_slice(ref.n_tiles, S)
+    rows = np.arange(ref.Q) if rows is None else np.asarray(rows, np.int64)
+    assert cnt.shape == (len(rows), S)
     for s in range(S):
         r0, r1 = X1.slice_rows(ref.n_tiles, S, s, ref.N)
-        for p in range(ref.Q):
+        for p, q in enumerate(rows):
             c = int(cnt[p, s])
             if c < 0:
                 assert c == -1
                 continue
             assert c <= ids.shape[2], f"{ctx}: query {p} slice {s}: count past the list"
-            nn = ref.nn_i[p, :min(int(ref.k[p]), ref.N)]
+            nn = ref.nn_i[q, :min(int(ref.k[q]), ref.N)]
             nn = nn[(nn >= r0) & (nn < r1)]
             lost = nn[~np.isin(nn, ids[p, s, :c])]
             assert len(lost) == 0, f"{ctx}: query {p} slice {s}: neighbours {lost.tolist()} not listed"
 
 
-def three_term(torch, src, ref, impl, cap, kmax, S, ctx, max_ovf_frac=0.05):
+def three_term(torch, src, ref, impl, cap, kmax, S, ctx, max_ovf_frac=0.05, qidx=None):
     """A 3-term screen and dmlp_refine on its lists: every list is complete or reports overflow
     (at most max_ovf_frac of the (query, slice) pairs); the refine hands back exactly the
     overflowed queries (status 1) and equals the oracle on every other."""
-    ops = Ops(torch, ref, src.labels)
+    ops = Ops(torch, ref, src.labels, qidx=qidx)
     L = ops.L
     er = np.float32(K.eps_rel(ref.A))
-    ids = torch.zeros(ref.Q * S * cap, dtype=torch.int32, device="cuda")
-    cnt = torch.full((ref.Q * S,), -7, dtype=torch.int32, device="cuda")
+    ls = Lists(torch, ops.nq, S, cap)     # (cand_h is not used: its NaNs must stay)
+    ids, cnt = ls.ids, ls.cnt
     head = (_p(ops.xfrag), _p(ops.xinit), ref.n_tiles, _p(ops.qhi), _p(ops.qlo), _p(ops.qn),
-            _p(ops.qidx), _p(ops.qk), ref.Q)
+            _p(ops.qidx), _p(ops.qk), ops.nq)
     tail = (ops.xnmax, ops.bad, er, S, _p(ids), _p(cnt), _stream(torch))
     if impl == "stream":
         assert cap == L.dmlp_screen_stream_cap(kmax) and L.dmlp_screen_stream_qw(ref.KT) > 0
@@ -514,18 +597,20 @@ def three_term(torch, src, ref, impl, cap, kmax, S, ctx, max_ovf_frac=0.05):
         assert kmax <= L.dmlp_screen_kmax(cap) and L.dmlp_screen_waves_hl(ref.KT, cap, 2) > 0
         _lib.check(L.dmlp_screen(ref.KT, cap, *head, *tail), "screen")
     torch.cuda.synchronize()
-    cnt_h = cnt.cpu().numpy().reshape(ref.Q, S)
+    ls.check_band(ctx)
+    ids_h, cnt_h, h_h = ls.host()
+    assert np.isnan(h_h).all()
     assert (cnt_h != -7).all()
-    check_id_lists(ref, ids.cpu().numpy().reshape(ref.Q, S, cap), cnt_h, S, ctx)
+    check_id_lists(ref, ids_h, cnt_h, S, ctx, rows=qidx)
     ovf = (cnt_h < 0).any(axis=1)
     assert (cnt_h < 0).sum() <= max_ovf_frac * cnt_h.size, \
         f"{ctx}: {(cnt_h < 0).sum()} of {cnt_h.size} (query, slice) pairs overflowed"
     out = Out(torch, ref.Q, kmax)
     _lib.check(L.dmlp_refine(cap, _p(ids), _p(cnt), S, _p(ops.X), ref.A, _p(ops.Qx), _p(ops.qidx),
-                             _p(ops.qk), ref.Q, _p(out.d), _p(out.i), out.kstride,
+                             _p(ops.qk), ops.nq, _p(out.d), _p(out.i), out.kstride,
                              *_label_args(ops, out, True), _p(out.status), _p(out.ovf),
                              _stream(torch)), "refine")
-    check_refined(ops, out, True, ctx + " refine", handed_back=ovf)
+    check_refined(ops, out, True, ctx + " refine", handed_back=ovf, rows=qidx)
 
 
 @pytest.mark.parametrize("data", ["uniform", "adversarial", "adversarial16"])
@@ -590,20 +675,9 @@ def lds_lists(ops, cap, kmax, S):
 
 def collect_lists(ops, k):
     """the two-pass large-k lists (dmlp_refine_groups2 collect = 1), as test_x1_two_pass"""
-    torch, L, ref = ops.torch, ops.L, ops.ref
     S1, S2, ccap = 16, 2, 1024
-    kp = ((np.maximum(ref.k, 1) + S1 - 1) // S1).astype(np.int32)
-    first = run_x1(ops, int(kp.max()), S1, qk=torch.from_numpy(kp).cuda())
-    hseed = torch.full((ref.Q,), float("nan"), dtype=torch.float32, device="cuda")
-    _lib.check(L.dmlp_x1_seed(_p(first.h), _p(first.cnt), S1, ref.Q, _p(hseed), _stream(torch)),
-               "x1_seed")
-    ls = Lists(torch, ref.Q, S2, ccap)
-    _lib.check(L.dmlp_screen_x1_collect(
-        ref.KT, ref.A, _p(ops.xfrag), _p(ops.xinit), ref.n_tiles, ref.N, _p(ops.qhi), _p(ops.qn),
-        _p(ops.qidx), _p(ops.qk), ref.Q, ops.xnmax, ops.bad, _p(hseed), ccap, S2, _p(ls.ids),
-        _p(ls.cnt), _p(ls.h), _stream(torch)), "screen_x1_collect")
-    torch.cuda.synchronize()
-    return ls
+    _, _, hseed = first_pass_seed(ops, S1)
+    return run_x1_collect(ops, hseed, ccap, S2)
 
 
 def vote_setup(torch, name):

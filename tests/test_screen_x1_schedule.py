@@ -122,11 +122,21 @@ class ModelLists:
     """The lists the screen's arithmetic gives without the MFMA's fp32 accumulation order: group
     maxima of fp32(a_model) floored to 16-bit keys, ak the k-th largest key of the slice's groups
     (when it has k of them; else no threshold), h = ak - 2 eps, every group whose key reaches
-    key(h) listed as key << 16 | group index."""
+    key(h) listed as key << 16 | group index.
+    rows: the query list (list position p holds the lists of reference row rows[p]; None: every
+    row in order).  eps_rows / k_rows: the rows eps and k are taken from (default rows; anything
+    else models a kernel that indexes them wrongly).  k: the k per row (default ref.k).
+    slack_keys: list down to that many 16-bit keys below key(h) (what a threshold lower by the
+    fp32 accumulation order's difference could add: how full the real lists can get)."""
 
-    def __init__(self, ref, S, cap, grows):
+    def __init__(self, ref, S, cap, grows, rows=None, eps_rows=None, k_rows=None, k=None,
+                 slack_keys=0):
         self.S, self.cap = S, cap
-        Q = ref.Q
+        rows = np.arange(ref.Q) if rows is None else np.asarray(rows, np.int64)
+        eps_of = ref.eps[rows if eps_rows is None else np.asarray(eps_rows, np.int64)]
+        k_of = np.asarray(ref.k if k is None else k)[rows if k_rows is None
+                                                     else np.asarray(k_rows, np.int64)]
+        Q = self.nq = len(rows)
         self.ids = np.zeros((Q, S, cap), np.int64)
         self.cnt = np.zeros((Q, S), np.int32)
         self.h = np.zeros((Q, S, 2), np.float32)
@@ -135,20 +145,20 @@ class ModelLists:
         for s in range(S):
             r0, r1 = X1.slice_rows(ref.n_tiles, S, s, ref.N)
             nts = max(0, min((s + 1) * tps, ref.n_tiles) - s * tps)
-            gm = X1.group_max(ref.a_model[:, r0:r1].astype(np.float32), nts, grows)
+            gm = X1.group_max(ref.a_model[rows][:, r0:r1].astype(np.float32), nts, grows)
             for p in range(Q):
                 real = np.nonzero(gm[p] > -np.inf)[0]
                 keys = X1.key16(gm[p, real])
-                kq, h = int(ref.k[p]), lowest
+                kq, h = int(k_of[p]), lowest
                 if 1 <= kq <= len(real):
                     ak = np.float32(X1.decode16(np.sort(keys)[-kq]))
-                    h = max(lowest, np.float32(ak - np.float32(2.0) * ref.eps[p]))
-                keep = keys >= X1.key16(np.array([h], np.float32))[0]
+                    h = max(lowest, np.float32(ak - np.float32(2.0) * eps_of[p]))
+                keep = keys >= X1.key16(np.array([h], np.float32))[0] - slack_keys
                 n = int(keep.sum())
                 assert n <= cap
                 self.ids[p, s, :n] = (keys[keep] << 16) | real[keep]
                 self.cnt[p, s] = n
-                self.h[p, s] = (h, ref.eps[p])
+                self.h[p, s] = (h, eps_of[p])
 
     def host(self):
         return self.ids, self.cnt, self.h
