@@ -331,15 +331,22 @@ extern "C" int dmlp_device_count(void) {
 }
 
 // Page-lock an existing host range (e.g. a node-shared /dev/shm mapping) so H2D copies from it
-// run as DMA at full PCIe rate.  Returns 0 or the hipError_t code.
+// run as DMA at full PCIe rate.  Returns 0 or the hipError_t code.  A refusal (a virtual machine
+// whose GPU cannot page-lock memory the process already has) is the caller's to handle — the
+// range stays pageable and copies from it are staged — so the runtime's last-error state is
+// cleared here: left set, the next launch check (DMLP_LAUNCH_CHECK, torch's) would report it.
 extern "C" int dmlp_host_register(void* p, int64_t bytes) {
   if (!p || bytes <= 0) return 0;
-  return (int)hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault);
+  const hipError_t e = hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return (int)e;
 }
 
 extern "C" int dmlp_host_unregister(void* p) {
   if (!p) return 0;
-  return (int)hipHostUnregister(p);
+  const hipError_t e = hipHostUnregister(p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return (int)e;
 }
 
 // Host render + H2D of the screen operands, the dataset part restricted to tiles [t0, t1): host
