@@ -132,6 +132,12 @@ _SIGS = {
     "dmlp_radius_components": (i32, [vp, i64, i32, C.c_double, vp, vp, vp]),
     "dmlp_set_components_order": (i32, [i32]),
     "dmlp_cpu_radius_components": (i32, [vp, i64, i32, C.c_double, vp, i32]),
+    "dmlp_kmeans_assign": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "dmlp_cluster_sums_bytes": (i64, [i64, i32, i32]),
+    "dmlp_cluster_sums": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "dmlp_set_kmeans_tile": (i32, [i32]),
+    "dmlp_cpu_kmeans_assign": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i32]),
+    "dmlp_cpu_cluster_sums": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32]),
     "dmlp_merge": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]),
     "dmlp_finalize": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
     "dmlp_vote_curve_kmax": (i32, []),

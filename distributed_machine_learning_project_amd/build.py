@@ -31,7 +31,9 @@ COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unus
 
 # screen_x1: fmaxf over MFMA results without the IEEE-mode NaN quieting (v_max_f32 x, x, x per
 # operand); the kernel never produces or compares NaN
-PER_FILE = {"screen_x1.hip": ["-fno-honor-nans"]}
+# kmeans.hip: built without the packed fp32 instructions (all of its arithmetic is fp64)
+PER_FILE = {"screen_x1.hip": ["-fno-honor-nans"],
+            "kmeans.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

@@ -300,6 +300,70 @@ extern "C" int dmlp_cpu_radius_components(const double* X, int64_t N, int A, dou
   return 0;
 }
 
+// dmlp_kmeans_assign on the host: the distance loop of dmlp_cpu_knn over the centroids in
+// ascending c, a strict < (NaN < x is false: a NaN ranks as +inf), label 0 with its distance as
+// computed where nothing is finite.
+extern "C" int dmlp_cpu_kmeans_assign(const double* X, int64_t N, int A, const double* C, int K,
+                                      const int* prev, int* label, double* dmin, int* changed,
+                                      int nthreads) {
+  if (N <= 0 || K <= 0) return 0;
+  if (N > INT32_MAX || K > INT32_MAX - 128 || A < 1 || !X || !C || !label || !dmin ||
+      (changed && !prev))
+    return -1;
+  parallel_for(N, default_threads(nthreads), [&](int64_t i) {
+    const double* x = X + i * A;
+    double bd = exact_dist(x, C, A);
+    int bc = 0;
+    for (int c = 1; c < K; ++c) {
+      const double d = exact_dist(x, C + (int64_t)c * A, A);
+      if (d < bd || (bd != bd && d < INFINITY)) {   // (a NaN at c = 0 yields to anything finite)
+        bd = d;
+        bc = c;
+      }
+    }
+    label[i] = bc;
+    dmin[i] = bd;
+  });
+  if (changed) {
+    int n = 0;
+    for (int64_t i = 0; i < N; ++i) n += label[i] != prev[i] ? 1 : 0;
+    *changed = n;
+  }
+  return 0;
+}
+
+// dmlp_cluster_sums on the host: cluster c's members perm[seg_off[c] .. seg_off[c + 1]) in runs of
+// 64, each run summed left to right from 0.0, the run sums added left to right from 0.0.
+extern "C" int dmlp_cpu_cluster_sums(const double* X, int64_t N, int A, int K, const double* extra,
+                                     const int* perm, const int64_t* seg_off, double* sums,
+                                     double* centroids_io, int nthreads) {
+  if (N <= 0 || K <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || !X || !perm || !seg_off || !sums) return -1;
+  const int T = A + (extra ? 1 : 0);
+  parallel_for(K, default_threads(nthreads), [&](int64_t c) {
+    double* out = sums + c * T;
+    for (int t = 0; t < T; ++t) out[t] = 0.0;
+    const int64_t b = seg_off[c], e = seg_off[c + 1];
+    if (b < 0 || e > N) return;
+    std::vector<double> run((size_t)T);
+    for (int64_t m0 = b; m0 < e; m0 += 64) {
+      const int64_t m1 = std::min(e, m0 + 64);
+      for (int t = 0; t < T; ++t) run[t] = 0.0;
+      for (int64_t m = m0; m < m1; ++m) {
+        const int id = perm[m];
+        if (id < 0 || id >= N) continue;
+        const double* x = X + (int64_t)id * A;
+        for (int t = 0; t < A; ++t) run[t] = run[t] + x[t];
+        if (extra) run[A] = run[A] + extra[id];
+      }
+      for (int t = 0; t < T; ++t) out[t] = out[t] + run[t];
+    }
+    if (centroids_io && e > b)
+      for (int t = 0; t < A; ++t) centroids_io[c * A + t] = out[t] / (double)(e - b);
+  });
+  return 0;
+}
+
 extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk,
                                  int64_t Q, const int* labels, int* out_label, uint64_t* out_cs) {
   (void)d;

@@ -557,6 +557,46 @@ int dmlp_radius_components(const double* X, int64_t N, int A, double r2, int* co
 // heaviest first, 0 in row order; the results are the same.  Returns the previous value.
 int dmlp_set_components_order(int heavy_first);
 
+// ---------------------------------------------------------------- device: k-means (kmeans.hip)
+// The two halves of a Lloyd iteration over rows X [N][A] and centroids C [K][A], d the contract's
+// distance above.  No FMA and no floating-point atomics: both are pure functions of their inputs,
+// bit-identical to the host twins.
+//   dmlp_kmeans_assign: label[i] = the smallest c in 0 .. K - 1 that minimises d(x_i, C_c); a NaN
+//     distance ranks as +inf.  So duplicate centroids resolve to the smaller index, and a row whose
+//     every distance is +inf or NaN gets label 0.  dmin[i] = the winner's distance as computed: it
+//     may be +inf or NaN.  With prev (nullable; must not overlap label) and changed (one device
+//     word; nullable, -1 when given without prev): *changed is SET to #{i : label[i] != prev[i]}
+//     (an integer atomic per wave).  Writes label[0 .. N) and dmin[0 .. N), nothing else.
+//   dmlp_cluster_sums: given labels in 0 .. K - 1 as their stable sort — perm [N]: the row ids
+//     ordered by (label, row id); seg_off [K + 1]: cluster c's members are perm[seg_off[c] ..
+//     seg_off[c + 1]); run_off [K + 1]: the exclusive prefix sum of ceil(count_c / 64) — the
+//     members of a cluster, in ascending row id, are cut into runs of 64 (the last may be
+//     shorter).  Each run is summed column by column, left to right, from 0.0; the run sums are
+//     then summed left to right, from 0.0.  The value row of member i is [x_i0 .. x_i,A-1], with
+//     extra[i] (nullable; the estimator's dmin) appended as column A: T = A + 1 columns, else T = A.
+//     sums [K][T]; an empty cluster's row is 0.0.  centroids_io (nullable) [K][A]: the Lloyd step —
+//     row c becomes sums[c, :A] / (double)count_c (IEEE division), count_c = seg_off[c + 1] -
+//     seg_off[c]; a cluster with count_c == 0 keeps its row.  ws: dmlp_cluster_sums_bytes(N, K, T)
+//     bytes, the run partials (N / 64 + K rows of T: no host sync for the number of runs).  Offsets
+//     that do not describe perm, or ids outside [0, N), read nothing out of bounds.
+// KMeans on top of them (models/kmeans.py): inertia_ is the left-to-right sum over c of sums[c, A];
+// a fit stops when an assignment changes no label, when the squared centroid shift (summed on the
+// host over the K x A centroids in row-major order) is <= tol, or at max_iter.
+// N <= 0 or K <= 0 returns 0 without a launch and writes nothing.  N > INT_MAX, K > INT_MAX - 128,
+// A < 1, a null pointer where none is allowed, or a workspace smaller than advertised return -1
+// before any launch; a launch failure returns -(int)hipError.
+int dmlp_kmeans_assign(const double* X, int64_t N, int A, const double* C, int K,
+                       const int* prev /*nullable*/, int* label, double* dmin,
+                       int* changed /*nullable*/, void* stream);
+int64_t dmlp_cluster_sums_bytes(int64_t N, int K, int T);
+int dmlp_cluster_sums(const double* X, int64_t N, int A, int K, const double* extra /*nullable*/,
+                      const int* perm, const int64_t* seg_off /*[K+1]*/,
+                      const int64_t* run_off /*[K+1]*/, void* ws, int64_t ws_bytes, double* sums,
+                      double* centroids_io /*nullable*/, void* stream);
+// A/B switch of tools/kmeans_bench.py: the assignment's tile, 1 (16-centroid tiles) or 8 (128),
+// anything else (the default) = chosen by K; the results are the same.  Returns the previous value.
+int dmlp_set_kmeans_tile(int pj);
+
 // ---------------------------------------------------------------- device: top-k merge (K4)
 // L sorted lists per query (list l of query q at in_*[l*list_stride + q*kin + j]), padded with
 // (+inf, -1); real entries may sit at distance +inf (id >= 0) and rank before the padding; only
@@ -724,6 +764,14 @@ int dmlp_cpu_radius_fill(const double* X, int64_t N, int A, const double* Qx, in
 // integers and the same argument checks.
 int dmlp_cpu_radius_components(const double* X, int64_t N, int A, double r2, int* comp,
                                int nthreads);
+// dmlp_kmeans_assign's and dmlp_cluster_sums' contracts on the host, threaded over the rows and
+// over the clusters: the same bits, the same argument checks (no workspace: a cluster's run sums
+// are added as they are formed, in run order).
+int dmlp_cpu_kmeans_assign(const double* X, int64_t N, int A, const double* C, int K,
+                           const int* prev, int* label, double* dmin, int* changed, int nthreads);
+int dmlp_cpu_cluster_sums(const double* X, int64_t N, int A, int K, const double* extra,
+                          const int* perm, const int64_t* seg_off, double* sums,
+                          double* centroids_io, int nthreads);
 int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,

@@ -1,4 +1,6 @@
-"""Model front-ends (exact k-NN classifier and regressor, serial KD-tree, DBSCAN)."""
+"""Model front-ends (exact k-NN classifier and regressor, serial KD-tree, DBSCAN, KMeans,
+NearestCentroid)."""
 from .dbscan import DBSCAN  # noqa: F401
+from .kmeans import KMeans, NearestCentroid  # noqa: F401
 from .knn_classifier import KDTree, KNNClassifier  # noqa: F401
 from .knn_regressor import KNNRegressor  # noqa: F401

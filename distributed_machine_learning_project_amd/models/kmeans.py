@@ -1,0 +1,151 @@
+"""KMeans (Lloyd) and NearestCentroid on the engine's distance, bit-identical on both devices.
+
+Two ops carry both estimators (ops.knn, csrc/kmeans.hip, dmlp.h "k-means"):
+  assign   label[i] = the SMALLEST c minimising d(x_i, C_c), d the engine's fp64 squared distance;
+           a NaN distance ranks as +inf, a row without a finite distance takes label 0
+  sums     per-cluster sums of the member rows in a FIXED order: members in ascending row id, cut
+           into runs of 64, a run summed left to right, the run sums added left to right — no
+           floating-point atomics, so the result does not change from run to run
+Lloyd step: centroid c = sums[c] / count[c] (IEEE division); an empty cluster keeps its centroid.
+The fit stops when an assignment changes no label, when the squared centroid shift — summed on the
+host over the K x A centroids in row-major order — is <= tol (tol > 0 only), or at max_iter.  Both
+devices hold identical centroids, so both stop at the same iteration.  labels_ and inertia_ always
+belong to cluster_centers_: inertia_ is the left-to-right sum over the clusters of the ordered sums
+of the members' distances.  On a GPU the rows go to the device once; per iteration only the
+changed count and, for tol > 0, the K x A centroids come back.
+
+Not offered yet: k-means++ seeding (its sampling needs a device prefix sum that cannot match the
+CPU bit for bit), n_init restarts, sample_weight, a multi-rank front end.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ..ops import knn as K
+from ..ops.knn import _torch
+
+
+def _sum_lr(v) -> float:
+    """((v_0 + v_1) + v_2) ...: np.add.accumulate is the sequential sum, np.sum is pairwise"""
+    v = np.asarray(v, np.float64).ravel()
+    return float(np.add.accumulate(v)[-1]) if v.size else 0.0
+
+
+class _Ops:
+    """assign / sums on host arrays or on one GPU, behind the same four calls"""
+
+    def __init__(self, device: str):
+        self.on_gpu = device == "gpu" or (device == "auto" and _torch().cuda.is_available())
+        self.assign = K.kmeans_assign_gpu if self.on_gpu else K.kmeans_assign_cpu
+        self.sums = K.cluster_sums_gpu if self.on_gpu else K.cluster_sums_cpu
+
+    def put(self, a):
+        return _torch().from_numpy(np.ascontiguousarray(a)).cuda() if self.on_gpu else a
+
+    def get(self, t):
+        return t.cpu().numpy() if self.on_gpu else t
+
+
+def _rows(X, name: str = "X", A=None):
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] < 1 or (A is not None and X.shape[1] != A):
+        raise ValueError(f"{name} must be [N, A]" + (" with A >= 1" if A is None else ""))
+    return X
+
+
+class KMeans:
+    def __init__(self, n_clusters: int, init, max_iter: int = 300, tol: float = 0.0,
+                 device: str = "auto"):
+        """init: a [K, A] array of centroids, "first" (rows 0 .. K - 1 of X), or an int seed (K
+        distinct rows of X drawn by numpy.random.default_rng(seed).choice, taken in ascending row
+        id)."""
+        for v, name in ((n_clusters, "n_clusters"), (max_iter, "max_iter")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1")
+        if not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0")
+        self.n_clusters, self.max_iter, self.tol = int(n_clusters), int(max_iter), float(tol)
+        self.init = init
+        self._ops = _Ops(device)
+        self.on_gpu = self._ops.on_gpu
+
+    def _init_centroids(self, X):
+        Kc, init = self.n_clusters, self.init
+        seed = isinstance(init, (int, np.integer)) and not isinstance(init, bool)
+        if isinstance(init, str) and init != "first":
+            raise ValueError('init must be a [K, A] array, "first" or an int seed')
+        if isinstance(init, str) or seed:
+            if X.shape[0] < Kc:
+                raise ValueError(f"{X.shape[0]} rows cannot seed {Kc} clusters")
+            rows = np.sort(np.random.default_rng(int(init)).choice(X.shape[0], Kc, replace=False)) \
+                if seed else np.arange(Kc)
+            return X[rows].copy()
+        C0 = np.array(init, np.float64, order="C")
+        if C0.shape != (Kc, X.shape[1]):
+            raise ValueError("an init array must be [n_clusters, A]")
+        return C0
+
+    def fit(self, X):
+        X = _rows(X)
+        if not X.shape[0]:
+            raise ValueError("X has no rows")
+        o, Kc, A = self._ops, self.n_clusters, X.shape[1]
+        Ch = self._init_centroids(X)        # the host's copy: the shift's "before"
+        Xd, C = o.put(X), o.put(Ch.copy())  # C is updated in place by the Lloyd step
+        prev, fresh, self.n_iter_ = None, False, 0
+        for it in range(self.max_iter):
+            label, dmin, changed = o.assign(Xd, C, prev)
+            if prev is not None and int(changed) == 0:
+                fresh = True                # label and dmin belong to C
+                break
+            o.sums(Xd, label, Kc, centroids=C)
+            self.n_iter_, prev = it + 1, label
+            if self.tol > 0.0:
+                Cn = o.get(C).copy()
+                diff = (Cn - Ch).ravel()
+                Ch = Cn
+                if _sum_lr(diff * diff) <= self.tol:
+                    break
+        if not fresh:
+            label, dmin, _ = o.assign(Xd, C)
+        sums, _ = o.sums(Xd, label, Kc, extra=dmin)
+        self.cluster_centers_ = o.get(C).copy()
+        self.labels_ = o.get(label)
+        self.inertia_ = _sum_lr(o.get(sums[:, A]))
+        return self
+
+    def fit_predict(self, X):
+        return self.fit(X).labels_
+
+    def predict(self, Q):
+        """int32 [Q]: the nearest centroid of each row, ties to the smaller cluster"""
+        Q = _rows(Q, "Q", self.cluster_centers_.shape[1])
+        o = self._ops
+        return o.get(o.assign(o.put(Q), o.put(self.cluster_centers_))[0])
+
+
+class NearestCentroid:
+    """The nearest-centroid classifier: centroids_ are the ORDERED class means (the ordered sums
+    of each class's rows over its count), predict the class of the nearest centroid.  A tie goes
+    to the SMALLER class — the assignment's rule, unlike the k-NN vote (larger label)."""
+
+    def __init__(self, device: str = "auto"):
+        self._ops = _Ops(device)
+        self.on_gpu = self._ops.on_gpu
+
+    def fit(self, X, y):
+        X = _rows(X)
+        y = np.asarray(y)
+        if y.shape != (X.shape[0],) or not X.shape[0]:
+            raise ValueError("y must be [N], N >= 1")
+        o = self._ops
+        self.classes_, rank = np.unique(y, return_inverse=True)
+        C = o.put(np.zeros((len(self.classes_), X.shape[1]), np.float64))
+        o.sums(o.put(X), o.put(rank.reshape(-1).astype(np.int32)), len(self.classes_), centroids=C)
+        self.centroids_ = o.get(C).copy()
+        return self
+
+    def predict(self, Q):
+        Q = _rows(Q, "Q", self.centroids_.shape[1])
+        o = self._ops
+        return self.classes_[o.get(o.assign(o.put(Q), o.put(self.centroids_))[0])]

@@ -446,6 +446,73 @@ def radius_components_cpu(X, r2, nthreads: int = 0):
     return comp
 
 
+def _kmeans_host_args(X, C):
+    X = np.ascontiguousarray(X, np.float64)
+    C = np.ascontiguousarray(C, np.float64)
+    if X.ndim != 2 or C.ndim != 2 or X.shape[1] != C.shape[1] or X.shape[1] < 1:
+        raise ValueError("X must be [N, A] and C [K, A] with A >= 1")
+    return X, C
+
+
+def kmeans_assign_cpu(X, C, prev=None, nthreads: int = 0):
+    """The assignment half of a Lloyd iteration (dmlp_cpu_kmeans_assign): label int32 [N], the
+    SMALLEST c minimising the engine's distance from row i of X [N, A] to row c of C [K, A] (a NaN
+    distance ranks as +inf; no finite distance: label 0), dmin float64 [N], the winner's distance
+    as computed, and changed = #{i : label[i] != prev[i]} (None without prev, int32 [N]).  K = 0
+    is a ValueError unless N = 0."""
+    X, Cn = _kmeans_host_args(X, C)
+    N, K = X.shape[0], Cn.shape[0]
+    if N and not K:
+        raise ValueError("no centroids")
+    label = np.zeros(N, np.int32)
+    dmin = np.zeros(N, np.float64)
+    changed = None
+    if prev is not None:
+        prev = np.ascontiguousarray(prev, np.int32)
+        if prev.shape != (N,):
+            raise ValueError("prev must be [N]")
+        changed = np.zeros(1, np.int32)
+    _lib.check(_lib.lib().dmlp_cpu_kmeans_assign(
+        X.ctypes.data, N, X.shape[1], Cn.ctypes.data, K, _np_ptr(prev), label.ctypes.data,
+        dmin.ctypes.data, _np_ptr(changed), nthreads), "cpu kmeans assign")
+    return label, dmin, None if changed is None else int(changed[0])
+
+
+def cluster_sums_cpu(X, label, K: int, extra=None, *, centroids=None, nthreads: int = 0):
+    """Ordered per-cluster sums (dmlp_cpu_cluster_sums): label int [N] in 0 .. K - 1; cluster c's
+    members in ascending row id — a STABLE sort of the labels — are cut into runs of 64, each run
+    summed left to right from 0.0 and the run sums added left to right from 0.0.  Returns (sums
+    float64 [K, T], count int64 [K]); the value row of member i is X[i], with extra[i] (float64
+    [N], e.g. kmeans_assign's dmin) appended as column A when given.  centroids (float64 [K, A],
+    C-contiguous, updated IN PLACE): the Lloyd step, row c = sums[c, :A] / count[c]; an empty
+    cluster keeps its row."""
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("X must be [N, A] with A >= 1")
+    N, A = X.shape
+    K = int(K)
+    label = np.ascontiguousarray(label, np.int32)
+    if label.shape != (N,) or K < 0 or (N and (label.min() < 0 or label.max() >= K)):
+        raise ValueError("label must be [N] with values in 0 .. K - 1")
+    if extra is not None:
+        extra = np.ascontiguousarray(extra, np.float64)
+        if extra.shape != (N,):
+            raise ValueError("extra must be [N]")
+    if centroids is not None and not (
+            isinstance(centroids, np.ndarray) and centroids.dtype == np.float64 and
+            centroids.shape == (K, A) and centroids.flags.c_contiguous):
+        raise ValueError("centroids must be a C-contiguous float64 [K, A] array")
+    perm = np.argsort(label, kind="stable").astype(np.int32)
+    count = np.bincount(label, minlength=K).astype(np.int64)
+    seg_off = np.zeros(K + 1, np.int64)
+    np.cumsum(count, out=seg_off[1:])
+    sums = np.zeros((K, A + (extra is not None)), np.float64)
+    _lib.check(_lib.lib().dmlp_cpu_cluster_sums(
+        X.ctypes.data, N, A, K, _np_ptr(extra), perm.ctypes.data, seg_off.ctypes.data,
+        sums.ctypes.data, _np_ptr(centroids), nthreads), "cpu cluster sums")
+    return sums, count
+
+
 # ======================================================================= GPU backend
 def _torch():
     import torch
@@ -1146,6 +1213,79 @@ def exact_nearest_gpu(X, Qx, qidx):
                                               _p(qk), len(qidx), 1, _p(d), _p(i), 1, _stream()),
                    "exact nearest")
     return d, i
+
+
+# ---------------------------------------------------------------- k-means: assignment, ordered sums
+def kmeans_assign_gpu(X, C, prev=None):
+    """kmeans_assign_cpu on the device (dmlp_kmeans_assign, csrc/kmeans.hip): X float64 [N, A] and
+    C float64 [K, A] tensors on one GPU (strided is fine), prev an int32 [N] tensor there or None.
+    Returns (label int32 [N], dmin float64 [N], changed): tensors there, the CPU's bits; changed
+    an int32 [1] tensor (None without prev) — reading it is the caller's host sync.  Asynchronous
+    on the current stream."""
+    torch = _torch()
+    X, C = _device_rows(X), _device_rows(C, "C")
+    if C.shape[1] != X.shape[1] or C.device != X.device:
+        raise ValueError("C must have X's attribute count and device")
+    N, K = X.shape[0], C.shape[0]
+    if N and not K:
+        raise ValueError("no centroids")
+    label = torch.zeros(N, dtype=torch.int32, device=X.device)
+    dmin = torch.zeros(N, dtype=torch.float64, device=X.device)
+    changed = None
+    if prev is not None:
+        if not torch.is_tensor(prev) or prev.dtype != torch.int32 or tuple(prev.shape) != (N,) or \
+                prev.device != X.device:
+            raise ValueError("prev must be an int32 [N] tensor on X's device")
+        prev = prev.contiguous()
+        changed = torch.zeros(1, dtype=torch.int32, device=X.device)
+    _lib.check(_lib.lib().dmlp_kmeans_assign(_p(X), N, X.shape[1], _p(C), K, _p(prev), _p(label),
+                                             _p(dmin), _p(changed), _stream()), "kmeans assign")
+    return label, dmin, changed
+
+
+def cluster_sums_gpu(X, label, K: int, extra=None, *, centroids=None):
+    """cluster_sums_cpu on the device (dmlp_cluster_sums): X a float64 [N, A] tensor on a GPU,
+    label an int32 [N] tensor there with values in 0 .. K - 1 (not checked: no host sync), extra a
+    float64 [N] tensor or None, centroids a contiguous float64 [K, A] tensor updated IN PLACE (the
+    Lloyd step) or None.  The membership plumbing stays in torch — a stable sort of the labels
+    (perm), bincount (count), integer cumulative sums (the cluster and run offsets); the sums are
+    the kernel's.  Returns (sums float64 [K, T], count int64 [K]) there, the CPU's bits.
+    Asynchronous on the current stream."""
+    torch = _torch()
+    L = _lib.lib()
+    X = _device_rows(X)
+    N, A = X.shape
+    K = int(K)
+    dev = X.device
+    if not torch.is_tensor(label) or label.dtype != torch.int32 or tuple(label.shape) != (N,) or \
+            label.device != dev or K < 0:
+        raise ValueError("label must be an int32 [N] tensor on X's device, K >= 0")
+    if extra is not None:
+        if not torch.is_tensor(extra) or extra.dtype != torch.float64 or \
+                tuple(extra.shape) != (N,) or extra.device != dev:
+            raise ValueError("extra must be a float64 [N] tensor on X's device")
+        extra = extra.contiguous()
+    if centroids is not None and not (
+            torch.is_tensor(centroids) and centroids.dtype == torch.float64 and
+            tuple(centroids.shape) == (K, A) and centroids.device == dev and
+            centroids.is_contiguous()):
+        raise ValueError("centroids must be a contiguous float64 [K, A] tensor on X's device")
+    T = A + (extra is not None)
+    sums = torch.zeros((K, T), dtype=torch.float64, device=dev)
+    if not N or not K:
+        return sums, torch.zeros(K, dtype=torch.int64, device=dev)
+    perm = torch.sort(label, stable=True).indices.to(torch.int32)
+    count = torch.bincount(label.long(), minlength=K)[:K]
+    seg_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    run_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(count, 0, out=seg_off[1:])
+    torch.cumsum((count + 63) // 64, 0, out=run_off[1:])
+    nbytes = L.dmlp_cluster_sums_bytes(N, K, T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.dmlp_cluster_sums(_p(X), N, A, K, _p(extra), _p(perm), _p(seg_off), _p(run_off),
+                                   _p(ws), nbytes, _p(sums), _p(centroids), _stream()),
+               "cluster sums")
+    return sums, count
 
 
 # ---------------------------------------------------------------- report text on the GPU
