@@ -136,6 +136,12 @@ _SIGS = {
     "dmlp_cluster_sums_bytes": (i64, [i64, i32, i32]),
     "dmlp_cluster_sums": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     "dmlp_set_kmeans_tile": (i32, [i32]),
+    "dmlp_kmeans_screen_rows_bytes": (i64, [i64, i32]),
+    "dmlp_kmeans_screen_prep_rows": (i32, [vp, i64, i32, vp, i64, vp]),
+    "dmlp_kmeans_screen_bytes": (i64, [i64, i32, i32]),
+    "dmlp_kmeans_screen_tile": (i32, [i32]),
+    "dmlp_kmeans_assign_screened": (i32, [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp,
+                                          i64, vp]),
     "dmlp_cpu_kmeans_assign": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i32]),
     "dmlp_cpu_cluster_sums": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32]),
     "dmlp_merge": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]),

@@ -597,6 +597,33 @@ int dmlp_cluster_sums(const double* X, int64_t N, int A, int K, const double* ex
 // anything else (the default) = chosen by K; the results are the same.  Returns the previous value.
 int dmlp_set_kmeans_tile(int pj);
 
+// ---------------------------------------------------------------- device: k-means, screened (kmeans_screen.hip)
+// A second way to dmlp_kmeans_assign's label, dmin and *changed, bit for bit: a single-term bf16
+// MFMA screen with dmlp_screen_x1_bound2(A, 2)'s bound keeps the centroids whose score is within
+// 2 eps of a row's best (up to 16 per row), their exact distances decide by the contract's rule.
+// A row whose list would overflow, a row outside the screen's range (a non-finite value, or
+// |x - mu| >= 1e15 in a column) and — when a centroid is outside it — every row is ESCALATED: the
+// fp64 tile of dmlp_kmeans_assign runs over a device-side list of those rows.  No host sync.
+//   rows: the row operands, dmlp_kmeans_screen_rows_bytes(N, A) bytes written by
+//     dmlp_kmeans_screen_prep_rows (mu by dmlp_center's rule, hi(x - mu) in bf16, |x - mu|^2 in
+//     fp32): made once per fit and valid for these X with any centroids.
+//   stats [2] device words, SET: rows escalated; candidates kept, summed over the other rows.
+//   ws: dmlp_kmeans_screen_bytes(N, A, K) bytes (the centroid operands, made on every call, the
+//     candidate lists and the escalation list).
+// Scope: 1 <= A <= 128, N <= INT_MAX, K <= INT_MAX - 128.  Outside it, with a null pointer
+// (prev and changed nullable as above) or a buffer smaller than advertised: -1 before any launch
+// (the _bytes functions return -1 as well); N <= 0 or K <= 0 returns 0 without a launch; a launch
+// failure returns -(int)hipError.  dmlp_kmeans_screen_tile(A): the centroids of one LDS tile.
+int64_t dmlp_kmeans_screen_rows_bytes(int64_t N, int A);
+int dmlp_kmeans_screen_prep_rows(const double* X, int64_t N, int A, void* rows, int64_t rows_bytes,
+                                 void* stream);
+int64_t dmlp_kmeans_screen_bytes(int64_t N, int A, int K);
+int dmlp_kmeans_screen_tile(int A);
+int dmlp_kmeans_assign_screened(const void* rows, int64_t rows_bytes, const double* X, int64_t N,
+                                int A, const double* C, int K, const int* prev /*nullable*/,
+                                int* label, double* dmin, int* changed /*nullable*/, int* stats,
+                                void* ws, int64_t ws_bytes, void* stream);
+
 // ---------------------------------------------------------------- device: top-k merge (K4)
 // L sorted lists per query (list l of query q at in_*[l*list_stride + q*kin + j]), padded with
 // (+inf, -1); real entries may sit at distance +inf (id >= 0) and rank before the padding; only

@@ -3,7 +3,8 @@
 //
 //   k_kmeans_assign<PJ>   label[i] = the smallest c minimising d(x_i, C_c), d the reference's fp64
 //     distance (fp64_tile.h).  The tile runs with the ROWS as its queries (64 per workgroup) and
-//     the K centroids as its data stream, PJ = 8 (128-centroid tiles, radius.hip's shape) or PJ = 1
+//     the K centroids as its data stream (kmeans_tile.h: the body, shared with the screened
+//     assignment's escalation kernel), PJ = 8 (128-centroid tiles, radius.hip's shape) or PJ = 1
 //     (16-centroid tiles: K = 8 or 16 pays for 16 columns, not 128).  None of the top-k tier's
 //     selection: a lane keeps ONE running (d, c) per row, taken by a strict < while its columns
 //     arrive in ascending c, so it holds its smallest c of the least distance; a NaN distance is
@@ -25,7 +26,7 @@
 //     in run order into sums[c, :], and on request the Lloyd step: centroid c = sums[c, :A] /
 //     (double)count, IEEE division; an empty cluster keeps its centroid.
 #include "dmlp.h"
-#include "fp64_tile.h"
+#include "kmeans_tile.h"
 #include <limits.h>
 #include <math.h>
 
@@ -36,65 +37,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PJ == 1 ? 4
 k_kmeans_assign(const double* __restrict__ X, int N, int A, const double* __restrict__ Cn, int K,
                 const int* __restrict__ prev, int* __restrict__ label, double* __restrict__ dmin,
                 int* changed) {
-  using Tl = dmlp::Fp64Tile<64, PJ, 16>;
-  constexpr int QB = Tl::QB, PT = Tl::PT, AS = Tl::AS, RI = Tl::RI;
-  __shared__ __attribute__((aligned(16))) double Qs[QB][AS];
-  __shared__ __attribute__((aligned(16))) double Xs[PT][AS];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int q0 = blockIdx.x * QB;
-  // this lane's best of row ty + 16 i so far: never a NaN, +inf until a finite distance arrives
-  double bd[RI];
-  int bc[RI];
-#pragma unroll
-  for (int i = 0; i < RI; ++i) {
-    bd[i] = INFINITY;
-    bc[i] = INT_MAX;
-  }
-
-  dmlp::fp64_tile_scan<Tl>(
-      Cn, (int64_t)K, A, X, q0, N, Qs, Xs, [](int qi) { return qi; },
-      [&](int64_t p0, const double (&acc)[RI][PJ]) __attribute__((always_inline)) {
-        // columns c = p0 + tx + 16 j ascend over j and over the tiles: strict < keeps the smaller
-        // c of equal distances; pads (c >= K) are no centroids; NaN < x is false
-#pragma unroll
-        for (int j = 0; j < PJ; ++j) {
-          const int c = (int)p0 + tx + 16 * j;
-#pragma unroll
-          for (int i = 0; i < RI; ++i) {
-            const bool take = c < K && acc[i][j] < bd[i];
-            bd[i] = take ? acc[i][j] : bd[i];
-            bc[i] = take ? c : bc[i];
-          }
-        }
-      });
-
-  int nch = 0;
-#pragma unroll
-  for (int i = 0; i < RI; ++i) {
-    double d = bd[i];
-    // a lane that saw no finite distance offers its smallest column at +inf (tx, when that is a
-    // centroid): a row without any finite distance ends at c = 0
-    int c = (bc[i] == INT_MAX && tx < K) ? tx : bc[i];
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {   // stays inside the row's 16 lanes
-      const double od = __shfl_xor(d, o);
-      const int oc = __shfl_xor(c, o);
-      const bool take = (od < d) | ((od == d) & (oc < c));
-      d = take ? od : d;
-      c = take ? oc : c;
-    }
-    const int q = q0 + ty + 16 * i;
-    const bool mine = tx == 0 && q < N;
-    bool ch = false;
-    if (mine) {
-      if (d == INFINITY) d = dmlp::exact_dist(X + (int64_t)q * A, Cn + (int64_t)c * A, A);
-      label[q] = c;
-      dmin[q] = d;
-      ch = prev != nullptr && prev[q] != c;
-    }
-    nch += __popcll(__ballot(ch));   // every lane of the wave reaches the ballot
-  }
-  if (changed != nullptr && nch != 0 && dmlp::lane_id() == 0) atomicAdd(changed, nch);
+  dmlp::kmeans_assign_tile<PJ>(X, A, Cn, K, prev, label, dmin, changed, blockIdx.x * 64, N,
+                               [](int qi) { return qi; });
 }
 
 __global__ void k_kmeans_zero(int* p) { *p = 0; }
@@ -173,10 +117,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void k_cluster_finish(
   }
 }
 
-// Centroid counts up to this take the 16-centroid tile: the largest measured K at which it beats
-// the 128-centroid tile (profiles/kmeans.md: ahead at K = 8, 16 and 64, behind at 256 and 1024;
-// nothing in between was measured)
-constexpr int kAssignNarrowK = 64;
+using dmlp::kAssignNarrowK;   // (kmeans_tile.h)
 int g_assign_pj = 0;   // 0: by K; 1 / 8: that tile (tools/kmeans_bench.py)
 
 int64_t max_runs(int64_t N, int K) { return N / 64 + K; }   // sum_c ceil(n_c / 64) <= N / 64 + K

@@ -14,8 +14,14 @@ belong to cluster_centers_: inertia_ is the left-to-right sum over the clusters 
 of the members' distances.  On a GPU the rows go to the device once; per iteration only the
 changed count and, for tol > 0, the K x A centroids come back.
 
+assign= chooses the GPU's way to the assignment, never its result: "exact" is the fp64 tile over
+all K centroids, "screen" the bf16 MFMA screen with an exact re-rank of its few candidates
+(csrc/kmeans_screen.hip; the row operands are made once per fit), "auto" the screen from
+K >= kAssignScreenK on.  A > 128 and the CPU always take the exact way.
+
 Not offered yet: k-means++ seeding (its sampling needs a device prefix sum that cannot match the
-CPU bit for bit), n_init restarts, sample_weight, a multi-rank front end.
+CPU bit for bit), n_init restarts, sample_weight, a multi-rank front end, a 3-term (hi/lo) screen
+for tightly packed centroids, the screen at A > 128.
 """
 from __future__ import annotations
 
@@ -31,13 +37,36 @@ def _sum_lr(v) -> float:
     return float(np.add.accumulate(v)[-1]) if v.size else 0.0
 
 
-class _Ops:
-    """assign / sums on host arrays or on one GPU, behind the same four calls"""
+# assign="auto" screens from this K on: the smallest measured K from which the screened assignment
+# is ahead of the exact one by more than the spread of both at every larger measured K
+# (profiles/kmeans_screen.md: ahead at K = 256, 1024 and 4096 for N = 1e5 and 1e6, A = 32 and 128;
+# at K = 64 behind at A = 128; nothing in between was measured)
+kAssignScreenK = 256
+kScreenMaxA = 128
 
-    def __init__(self, device: str):
+
+class _Ops:
+    """assign / sums on host arrays or on one GPU, behind the same calls"""
+
+    def __init__(self, device: str, assign: str = "auto"):
+        if assign not in ("exact", "screen", "auto"):
+            raise ValueError('assign must be "exact", "screen" or "auto"')
         self.on_gpu = device == "gpu" or (device == "auto" and _torch().cuda.is_available())
-        self.assign = K.kmeans_assign_gpu if self.on_gpu else K.kmeans_assign_cpu
+        self.mode = assign
         self.sums = K.cluster_sums_gpu if self.on_gpu else K.cluster_sums_cpu
+
+    def rows(self, Xd, Kc: int):
+        """what assign takes for these rows against Kc centroids: the rows themselves, or — where
+        the choice is the screen — its row operands around them, made here once"""
+        screen = self.on_gpu and Xd.shape[1] <= kScreenMaxA and (
+            self.mode == "screen" or
+            (self.mode == "auto" and kAssignScreenK is not None and Kc >= kAssignScreenK))
+        return K.kmeans_rows_gpu(Xd) if screen else Xd
+
+    def assign(self, Xr, C, prev=None):
+        if not self.on_gpu:
+            return K.kmeans_assign_cpu(Xr, C, prev)
+        return K.kmeans_assign_gpu(Xr, C, prev, screen=isinstance(Xr, K.KMeansRows))
 
     def put(self, a):
         return _torch().from_numpy(np.ascontiguousarray(a)).cuda() if self.on_gpu else a
@@ -55,7 +84,7 @@ def _rows(X, name: str = "X", A=None):
 
 class KMeans:
     def __init__(self, n_clusters: int, init, max_iter: int = 300, tol: float = 0.0,
-                 device: str = "auto"):
+                 device: str = "auto", assign: str = "auto"):
         """init: a [K, A] array of centroids, "first" (rows 0 .. K - 1 of X), or an int seed (K
         distinct rows of X drawn by numpy.random.default_rng(seed).choice, taken in ascending row
         id)."""
@@ -66,7 +95,7 @@ class KMeans:
             raise ValueError("tol must be >= 0")
         self.n_clusters, self.max_iter, self.tol = int(n_clusters), int(max_iter), float(tol)
         self.init = init
-        self._ops = _Ops(device)
+        self._ops = _Ops(device, assign)
         self.on_gpu = self._ops.on_gpu
 
     def _init_centroids(self, X):
@@ -92,9 +121,10 @@ class KMeans:
         o, Kc, A = self._ops, self.n_clusters, X.shape[1]
         Ch = self._init_centroids(X)        # the host's copy: the shift's "before"
         Xd, C = o.put(X), o.put(Ch.copy())  # C is updated in place by the Lloyd step
+        Xr = o.rows(Xd, Kc)
         prev, fresh, self.n_iter_ = None, False, 0
         for it in range(self.max_iter):
-            label, dmin, changed = o.assign(Xd, C, prev)
+            label, dmin, changed = o.assign(Xr, C, prev)
             if prev is not None and int(changed) == 0:
                 fresh = True                # label and dmin belong to C
                 break
@@ -107,7 +137,7 @@ class KMeans:
                 if _sum_lr(diff * diff) <= self.tol:
                     break
         if not fresh:
-            label, dmin, _ = o.assign(Xd, C)
+            label, dmin, _ = o.assign(Xr, C)
         sums, _ = o.sums(Xd, label, Kc, extra=dmin)
         self.cluster_centers_ = o.get(C).copy()
         self.labels_ = o.get(label)
@@ -121,7 +151,8 @@ class KMeans:
         """int32 [Q]: the nearest centroid of each row, ties to the smaller cluster"""
         Q = _rows(Q, "Q", self.cluster_centers_.shape[1])
         o = self._ops
-        return o.get(o.assign(o.put(Q), o.put(self.cluster_centers_))[0])
+        Qr = o.rows(o.put(Q), self.n_clusters)
+        return o.get(o.assign(Qr, o.put(self.cluster_centers_))[0])
 
 
 class NearestCentroid:
@@ -129,8 +160,8 @@ class NearestCentroid:
     of each class's rows over its count), predict the class of the nearest centroid.  A tie goes
     to the SMALLER class — the assignment's rule, unlike the k-NN vote (larger label)."""
 
-    def __init__(self, device: str = "auto"):
-        self._ops = _Ops(device)
+    def __init__(self, device: str = "auto", assign: str = "auto"):
+        self._ops = _Ops(device, assign)
         self.on_gpu = self._ops.on_gpu
 
     def fit(self, X, y):
@@ -148,4 +179,5 @@ class NearestCentroid:
     def predict(self, Q):
         Q = _rows(Q, "Q", self.centroids_.shape[1])
         o = self._ops
-        return self.classes_[o.get(o.assign(o.put(Q), o.put(self.centroids_))[0])]
+        Qr = o.rows(o.put(Q), len(self.classes_))
+        return self.classes_[o.get(o.assign(Qr, o.put(self.centroids_))[0])]

@@ -1216,14 +1216,52 @@ def exact_nearest_gpu(X, Qx, qidx):
 
 
 # ---------------------------------------------------------------- k-means: assignment, ordered sums
-def kmeans_assign_gpu(X, C, prev=None):
+class KMeansRows:
+    """Rows on a GPU with the screened assignment's row operands (kmeans_rows_gpu): X, and the
+    device buffer holding mu, hi(x - mu) in bf16 and |x - mu|^2.  Valid for these rows with any
+    centroids; None as the buffer when the screen does not serve the shape (A > 128)."""
+
+    def __init__(self, X, buf):
+        self.X, self.buf = X, buf
+
+    @property
+    def mu(self):
+        torch = _torch()
+        return None if self.buf is None else \
+            self.buf[:8 * self.X.shape[1]].view(torch.float64).clone()
+
+
+def kmeans_rows_gpu(X):
+    """The once-per-fit half of the screened assignment (dmlp_kmeans_screen_prep_rows,
+    csrc/kmeans_screen.hip) for X float64 [N, A] on a GPU: a KMeansRows to pass as
+    kmeans_assign_gpu's X.  Asynchronous on the current stream."""
+    torch = _torch()
+    L = _lib.lib()
+    X = _device_rows(X)
+    N, A = X.shape
+    nbytes = L.dmlp_kmeans_screen_rows_bytes(N, A)
+    if nbytes < 0:
+        return KMeansRows(X, None)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    _lib.check(L.dmlp_kmeans_screen_prep_rows(_p(X), N, A, _p(buf), nbytes, _stream()),
+               "kmeans screen rows")
+    return KMeansRows(X, buf)
+
+
+def kmeans_assign_gpu(X, C, prev=None, *, screen=False, stats=False):
     """kmeans_assign_cpu on the device (dmlp_kmeans_assign, csrc/kmeans.hip): X float64 [N, A] and
     C float64 [K, A] tensors on one GPU (strided is fine), prev an int32 [N] tensor there or None.
     Returns (label int32 [N], dmin float64 [N], changed): tensors there, the CPU's bits; changed
     an int32 [1] tensor (None without prev) — reading it is the caller's host sync.  Asynchronous
-    on the current stream."""
+    on the current stream.
+    screen=True takes the screened way to the same bits (dmlp_kmeans_assign_screened,
+    csrc/kmeans_screen.hip): X may then be a KMeansRows (kmeans_rows_gpu: the row operands made
+    once); a tensor is prepared on the fly.  A shape the screen does not serve (A > 128) takes the
+    exact kernel.  stats=True appends an int32 [2] tensor: rows escalated to the exact kernel and
+    candidates kept over the other rows (zeros where the screen did not run)."""
     torch = _torch()
-    X, C = _device_rows(X), _device_rows(C, "C")
+    rows = X if isinstance(X, KMeansRows) else None
+    X, C = _device_rows(rows.X if rows else X), _device_rows(C, "C")
     if C.shape[1] != X.shape[1] or C.device != X.device:
         raise ValueError("C must have X's attribute count and device")
     N, K = X.shape[0], C.shape[0]
@@ -1231,6 +1269,7 @@ def kmeans_assign_gpu(X, C, prev=None):
         raise ValueError("no centroids")
     label = torch.zeros(N, dtype=torch.int32, device=X.device)
     dmin = torch.zeros(N, dtype=torch.float64, device=X.device)
+    st = torch.zeros(2, dtype=torch.int32, device=X.device) if stats else None
     changed = None
     if prev is not None:
         if not torch.is_tensor(prev) or prev.dtype != torch.int32 or tuple(prev.shape) != (N,) or \
@@ -1238,9 +1277,23 @@ def kmeans_assign_gpu(X, C, prev=None):
             raise ValueError("prev must be an int32 [N] tensor on X's device")
         prev = prev.contiguous()
         changed = torch.zeros(1, dtype=torch.int32, device=X.device)
-    _lib.check(_lib.lib().dmlp_kmeans_assign(_p(X), N, X.shape[1], _p(C), K, _p(prev), _p(label),
-                                             _p(dmin), _p(changed), _stream()), "kmeans assign")
-    return label, dmin, changed
+    L = _lib.lib()
+    done = False
+    if screen and N and K:
+        rows = rows or kmeans_rows_gpu(X)
+        nbytes = L.dmlp_kmeans_screen_bytes(N, X.shape[1], K)
+        if rows.buf is not None and nbytes >= 0:
+            st = st if st is not None else torch.zeros(2, dtype=torch.int32, device=X.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+            _lib.check(L.dmlp_kmeans_assign_screened(
+                _p(rows.buf), rows.buf.numel(), _p(X), N, X.shape[1], _p(C), K, _p(prev),
+                _p(label), _p(dmin), _p(changed), _p(st), _p(ws), nbytes, _stream()),
+                "kmeans assign (screened)")
+            done = True
+    if not done:
+        _lib.check(L.dmlp_kmeans_assign(_p(X), N, X.shape[1], _p(C), K, _p(prev), _p(label),
+                                        _p(dmin), _p(changed), _stream()), "kmeans assign")
+    return (label, dmin, changed, st) if stats else (label, dmin, changed)
 
 
 def cluster_sums_gpu(X, label, K: int, extra=None, *, centroids=None):
