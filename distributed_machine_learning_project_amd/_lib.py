@@ -140,6 +140,7 @@ _SIGS = {
     "dmlp_kmeans_screen_prep_rows": (i32, [vp, i64, i32, vp, i64, vp]),
     "dmlp_kmeans_screen_bytes": (i64, [i64, i32, i32]),
     "dmlp_kmeans_screen_tile": (i32, [i32]),
+    "dmlp_kmeans_screen_layout": (i32, [i64, i32, i32, i64p, i64p]),
     "dmlp_kmeans_assign_screened": (i32, [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp,
                                           i64, vp]),
     "dmlp_cpu_kmeans_assign": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i32]),

@@ -619,6 +619,13 @@ int dmlp_kmeans_screen_prep_rows(const double* X, int64_t N, int A, void* rows, 
                                  void* stream);
 int64_t dmlp_kmeans_screen_bytes(int64_t N, int A, int K);
 int dmlp_kmeans_screen_tile(int A);
+// Where the operands and lists lie, for readers of a finished call (tests): rows_off = the byte
+// offsets of hi(x - mu) ([N][KT][4] 16-byte words) and |x - mu|^2 (fp32 [N]) in rows (mu, A
+// doubles, is at 0); ws_off = the byte offsets in ws of cnt (int [N]: candidates of a row, -1:
+// escalated), esc (int [N]: the stats[0] escalated row ids) and cand (int [N][16], ascending);
+// the first word of ws holds the rounded-up max |c - mu|^2 (fp32 bits) that eps was made from.
+// Returns 0, or -1 where the _bytes functions do or for a null pointer.
+int dmlp_kmeans_screen_layout(int64_t N, int A, int K, int64_t rows_off[2], int64_t ws_off[3]);
 int dmlp_kmeans_assign_screened(const void* rows, int64_t rows_bytes, const double* X, int64_t N,
                                 int A, const double* C, int K, const int* prev /*nullable*/,
                                 int* label, double* dmin, int* changed /*nullable*/, int* stats,

@@ -386,6 +386,20 @@ extern "C" int64_t dmlp_kmeans_screen_bytes(int64_t N, int A, int K) {
   return carve(nullptr, N, (A + 31) / 32, K).bytes;
 }
 
+extern "C" int dmlp_kmeans_screen_layout(int64_t N, int A, int K, int64_t rows_off[2],
+                                         int64_t ws_off[3]) {
+  if (!screen_shape_ok(N, A, K) || !rows_off || !ws_off) return -1;
+  const int KT = (A + 31) / 32;
+  const Ws w = carve(nullptr, N, KT, K);
+  rows_off[0] = kMuBytes;
+  rows_off[1] = kMuBytes + up256(N * KT * 64);
+  const char* const base = (const char*)w.words;   // (carve puts words at offset 0)
+  ws_off[0] = (const char*)w.cnt - base;
+  ws_off[1] = (const char*)w.esc - base;
+  ws_off[2] = (const char*)w.cand - base;
+  return 0;
+}
+
 extern "C" int dmlp_kmeans_screen_prep_rows(const double* X, int64_t N, int A, void* rows,
                                             int64_t rows_bytes, void* stream) {
   if (N == 0) return 0;
