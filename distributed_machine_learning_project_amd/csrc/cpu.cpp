@@ -364,6 +364,80 @@ extern "C" int dmlp_cpu_cluster_sums(const double* X, int64_t N, int A, int K, c
   return 0;
 }
 
+namespace {
+
+// dmlp_kmeans_seed's walk over items 0 .. n - 1 (val(i) >= +0.0) with the running sum s: the first
+// item with s + val > t, s left as it stood before it; else the last item with val > 0 (0 when
+// there is none), s the sum over all items.
+template <class Val>
+int64_t seed_walk(int64_t n, Val val, double& s, double t) {
+  int64_t fb = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const double x = val(i), next = s + x;
+    if (next > t) return i;
+    if (x > 0.0) fb = i;
+    s = next;
+  }
+  return fb;
+}
+
+}  // namespace
+
+// dmlp_kmeans_seed on the host: the update threaded over the runs of 64 rows, the block sums, the
+// total and the walk serial, the same operations in the same order.
+extern "C" int dmlp_cpu_kmeans_seed(const double* X, int64_t N, int A, int K, int i0,
+                                    const double* u, int* seeds, double* C, double* w,
+                                    int nthreads) {
+  if (N <= 0 || K <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || i0 < 0 || i0 >= N || !X || (K > 1 && !u) || !seeds || !C || !w)
+    return -1;
+  const int64_t nruns = (N + 63) / 64, nblocks = (nruns + 63) / 64;
+  std::vector<double> R((size_t)nruns), B((size_t)nblocks);
+  const int nt = default_threads(nthreads);
+  for (int64_t i = 0; i < N; ++i) w[i] = INFINITY;
+  auto update = [&](const double* c) {
+    parallel_for(nruns, nt, [&](int64_t r) {
+      double s = 0.0;
+      for (int64_t i = r * 64; i < std::min(N, r * 64 + 64); ++i) {
+        const double d = exact_dist(X + i * A, c, A);
+        w[i] = d < w[i] ? d : w[i];
+        s = s + (w[i] < INFINITY ? w[i] : 0.0);
+      }
+      R[r] = s;
+    });
+  };
+  auto take = [&](int j, int64_t row) {
+    seeds[j] = (int)row;
+    std::memcpy(C + (int64_t)j * A, X + row * A, sizeof(double) * A);
+  };
+  take(0, i0);
+  for (int j = 1; j < K; ++j) {
+    update(C + (int64_t)(j - 1) * A);
+    double T = 0.0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+      double s = 0.0;
+      for (int64_t r = b * 64; r < std::min(nruns, b * 64 + 64); ++r) s = s + R[r];
+      B[b] = s;
+      T = T + s;
+    }
+    if (!(T > 0.0 && T < INFINITY)) {
+      const double p = u[j - 1] * (double)N;
+      take(j, p >= 0.0 ? (p < (double)N ? (int64_t)p : N - 1) : 0);   // (a NaN u: row 0)
+      continue;
+    }
+    const double t = u[j - 1] * T;
+    double s = 0.0;
+    const int64_t b = seed_walk(nblocks, [&](int64_t i) { return B[i]; }, s, t);
+    const int64_t r = b * 64 + seed_walk(std::min<int64_t>(64, nruns - b * 64),
+                                         [&](int64_t i) { return R[b * 64 + i]; }, s, t);
+    take(j, r * 64 + seed_walk(std::min<int64_t>(64, N - r * 64), [&](int64_t i) {
+           const double wi = w[r * 64 + i];
+           return wi < INFINITY ? wi : 0.0; }, s, t));
+  }
+  update(C + (int64_t)(K - 1) * A);
+  return 0;
+}
+
 extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk,
                                  int64_t Q, const int* labels, int* out_label, uint64_t* out_cs) {
   (void)d;

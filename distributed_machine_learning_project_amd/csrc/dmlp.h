@@ -597,6 +597,42 @@ int dmlp_cluster_sums(const double* X, int64_t N, int A, int K, const double* ex
 // anything else (the default) = chosen by K; the results are the same.  Returns the previous value.
 int dmlp_set_kmeans_tile(int pj);
 
+// ---------------------------------------------------------------- device: k-means seeding (kmeans_seed.hip)
+// D^2 (k-means++) seeding, the same words for dmlp_kmeans_seed and dmlp_cpu_kmeans_seed: a pure
+// function of its inputs, bit-identical on both devices.  Takes rows X [N][A], K >= 1, a first row
+// id i0 in [0, N) and u [K - 1] doubles with 0 <= u < 1 (in device memory for the device entry;
+// not read, and nullable, at K = 1).  Writes seeds (int32 [K], row ids), C [K][A] (C[j] =
+// X[seeds[j]], copied bits) and w [N] (each row's distance to its nearest seed, as computed).
+// seeds[0] = i0 and w_i starts at +inf.  For j = 1 .. K - 1:
+//   1. Update.  d = d(x_i, C[j - 1]), the contract's distance above (left to right, each sub, mul
+//      and add rounded separately, no FMA); w_i = d < w_i ? d : w_i, so a NaN d leaves w_i.  The
+//      sampling weight is v_i = w_i < +inf ? w_i : 0.0.
+//   2. Fixed-order sums.  Rows are cut into runs of 64 (run r: rows 64r .. 64r + 63, the last may
+//      be short), runs into blocks of 64 runs (4096 rows).  R_r = the left-to-right sum of v over
+//      the run, from 0.0; B_b = the left-to-right sum of R_r over the block, from 0.0; T = the
+//      left-to-right sum of B_b, from 0.0.
+//   3. Pick.  If not 0 < T < +inf: seeds[j] = (int)(u_j * N) — the degenerate case; a duplicate
+//      seed is allowed there and only there.  Otherwise t = u_j * T (one rounded multiply), s =
+//      0.0, and the blocks are walked in ascending order: the first block with s + B_b > t is
+//      entered, s unchanged; a block that is passed leaves s = s + B_b.  If no block qualifies,
+//      the last block with B_b > 0 is entered, and s stays the sum over all blocks: s is never
+//      rewound.  The entered block's runs are walked the same way with that running s (s + R_r >
+//      t; else the last run with R_r > 0, s then the sum over the block's runs as well), then the
+//      entered run's rows (s + v_i > t; else the last row with v_i > 0).  That row is seeds[j].
+//      Only additions, never a subtraction.  The picked row has v_i > 0: it is no earlier seed.
+// After the last pick one more update against C[K - 1]: w belongs to all K seeds.
+// u outside [0, 1) is the caller's error (ops.knn checks it on the host); the picked row is
+// clamped into [0, N) whatever u holds, a NaN product picks row 0.
+// 2K launches on the caller's stream, no host sync.  ws: dmlp_kmeans_seed_bytes(N) bytes —
+// ceil(N / 64) run sums and ceil(N / 4096) block sums (-1 for N < 0 or N > INT_MAX).
+// N <= 0 or K <= 0 returns 0, launches nothing and writes nothing.  N > INT_MAX, A < 1, i0
+// outside [0, N), a null pointer (u at K = 1 excepted) or a workspace smaller than advertised
+// return -1 before any launch; a launch failure returns -(int)hipError.
+int64_t dmlp_kmeans_seed_bytes(int64_t N);
+int dmlp_kmeans_seed(const double* X, int64_t N, int A, int K, int i0, const double* u /*[K-1]*/,
+                     int* seeds /*[K]*/, double* C /*[K][A]*/, double* w /*[N]*/, void* ws,
+                     int64_t ws_bytes, void* stream);
+
 // ---------------------------------------------------------------- device: k-means, screened (kmeans_screen.hip)
 // A second way to dmlp_kmeans_assign's label, dmin and *changed, bit for bit: a single-term bf16
 // MFMA screen with dmlp_screen_x1_bound2(A, 2)'s bound keeps the centroids whose score is within
@@ -806,6 +842,10 @@ int dmlp_cpu_kmeans_assign(const double* X, int64_t N, int A, const double* C, i
 int dmlp_cpu_cluster_sums(const double* X, int64_t N, int A, int K, const double* extra,
                           const int* perm, const int64_t* seg_off, double* sums,
                           double* centroids_io, int nthreads);
+// dmlp_kmeans_seed's contract on the host (u in host memory, no workspace): the update threaded
+// over the runs, the sums and the walk serial; the same bits, the same argument checks.
+int dmlp_cpu_kmeans_seed(const double* X, int64_t N, int A, int K, int i0, const double* u,
+                         int* seeds, double* C, double* w, int nthreads);
 int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,

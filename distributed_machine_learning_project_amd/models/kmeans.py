@@ -19,9 +19,18 @@ all K centroids, "screen" the bf16 MFMA screen with an exact re-rank of its few 
 (csrc/kmeans_screen.hip; the row operands are made once per fit), "auto" the screen from
 K >= kAssignScreenK on.  A > 128 and the CPU always take the exact way.
 
-Not offered yet: k-means++ seeding (its sampling needs a device prefix sum that cannot match the
-CPU bit for bit), n_init restarts, sample_weight, a multi-rank front end, a 3-term (hi/lo) screen
-for tightly packed centroids, the screen at A > 128.
+seeding="d2" with init=<int seed> is k-means++ seeding (ops.knn.kmeans_seed_*, csrc/kmeans_seed.hip,
+dmlp.h "k-means seeding"): the first seed is row i0, each further one the row at which the running
+sum of the rows' distances to their nearest seed so far passes u times its total.  The sums run in
+a fixed order (runs of 64 rows, blocks of 64 runs, the blocks left to right), so both devices pick
+the same rows; the draws come from the host: rng = numpy.random.default_rng(seed), i0 =
+int(rng.integers(N)), u = rng.random(K - 1).  On a GPU the rows go over first and the K seeds are
+picked there without a host sync.  The spelling is a keyword of its own because the string init
+"k-means++" has always been a ValueError here and stays one; seeding="uniform" (the default) is
+the draw of K distinct rows, as before.
+
+Not offered yet: greedy k-means++ (local trials), n_init restarts, sample_weight, a multi-rank
+front end, a 3-term (hi/lo) screen for tightly packed centroids, the screen at A > 128.
 """
 from __future__ import annotations
 
@@ -84,23 +93,43 @@ def _rows(X, name: str = "X", A=None):
 
 class KMeans:
     def __init__(self, n_clusters: int, init, max_iter: int = 300, tol: float = 0.0,
-                 device: str = "auto", assign: str = "auto"):
+                 device: str = "auto", assign: str = "auto", seeding: str = "uniform"):
         """init: a [K, A] array of centroids, "first" (rows 0 .. K - 1 of X), or an int seed (K
         distinct rows of X drawn by numpy.random.default_rng(seed).choice, taken in ascending row
-        id)."""
+        id).  seeding="d2", with an int seed only: D^2 (k-means++) seeding from that generator;
+        seed_rows_ then holds the K seed rows."""
         for v, name in ((n_clusters, "n_clusters"), (max_iter, "max_iter")):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1")
         if not float(tol) >= 0.0:
             raise ValueError("tol must be >= 0")
         self.n_clusters, self.max_iter, self.tol = int(n_clusters), int(max_iter), float(tol)
-        self.init = init
+        if seeding not in ("uniform", "d2"):
+            raise ValueError('seeding must be "uniform" or "d2"')
+        if seeding == "d2" and not self._is_seed(init):
+            raise ValueError('seeding="d2" needs init=<int seed>')
+        self.init, self.seeding = init, seeding
         self._ops = _Ops(device, assign)
         self.on_gpu = self._ops.on_gpu
 
+    @staticmethod
+    def _is_seed(init) -> bool:
+        return isinstance(init, (int, np.integer)) and not isinstance(init, bool)
+
+    def _seed_d2(self, Xd):
+        """(seeds, C) where Xd lies: the D^2 seeding of the rows from init's generator"""
+        N, Kc = Xd.shape[0], self.n_clusters
+        if N < Kc:
+            raise ValueError(f"{N} rows cannot seed {Kc} clusters")
+        rng = np.random.default_rng(int(self.init))
+        i0 = int(rng.integers(N))
+        u = rng.random(Kc - 1)
+        seed = K.kmeans_seed_gpu if self.on_gpu else K.kmeans_seed_cpu
+        return seed(Xd, Kc, i0, u)[:2]
+
     def _init_centroids(self, X):
         Kc, init = self.n_clusters, self.init
-        seed = isinstance(init, (int, np.integer)) and not isinstance(init, bool)
+        seed = self._is_seed(init)
         if isinstance(init, str) and init != "first":
             raise ValueError('init must be a [K, A] array, "first" or an int seed')
         if isinstance(init, str) or seed:
@@ -119,8 +148,14 @@ class KMeans:
         if not X.shape[0]:
             raise ValueError("X has no rows")
         o, Kc, A = self._ops, self.n_clusters, X.shape[1]
-        Ch = self._init_centroids(X)        # the host's copy: the shift's "before"
-        Xd, C = o.put(X), o.put(Ch.copy())  # C is updated in place by the Lloyd step
+        if self.seeding == "d2":
+            Xd = o.put(X)                   # the rows go over first: the seeds are picked there
+            seeds, C = self._seed_d2(Xd)    # C is updated in place by the Lloyd step
+            self.seed_rows_ = o.get(seeds)
+            Ch = o.get(C).copy()            # the host's copy: the shift's "before"
+        else:
+            Ch = self._init_centroids(X)
+            Xd, C = o.put(X), o.put(Ch.copy())
         Xr = o.rows(Xd, Kc)
         prev, fresh, self.n_iter_ = None, False, 0
         for it in range(self.max_iter):

@@ -7,4 +7,4 @@ from .knn import (knn_cpu, finalize_cpu, merge_cpu, prepare_dataset, knn_gpu,  #
                   radius_count_cpu, radius_cpu, radius_count_gpu, radius_gpu,
                   radius_components_cpu, radius_components_gpu, exact_nearest_gpu,
                   kmeans_assign_cpu, kmeans_assign_gpu, kmeans_rows_gpu, cluster_sums_cpu,
-                  cluster_sums_gpu)
+                  cluster_sums_gpu, kmeans_seed_cpu, kmeans_seed_gpu)

@@ -513,6 +513,35 @@ def cluster_sums_cpu(X, label, K: int, extra=None, *, centroids=None, nthreads: 
     return sums, count
 
 
+def _seed_args(N: int, K, i0, u):
+    """(K, i0, u float64 [K - 1]) of a D^2 seeding over N rows, checked on the host"""
+    K, i0 = int(K), int(i0)
+    u = np.ascontiguousarray(u, np.float64)
+    if K < 1 or not 0 <= i0 < N:
+        raise ValueError("K must be >= 1 and i0 a row id in [0, N)")
+    if u.shape != (K - 1,) or not ((u >= 0.0) & (u < 1.0)).all():
+        raise ValueError("u must be [K - 1] with 0 <= u < 1")
+    return K, i0, u
+
+
+def kmeans_seed_cpu(X, K: int, i0: int, u, nthreads: int = 0):
+    """D^2 (k-means++) seeding by dmlp.h's fixed-order contract (dmlp_cpu_kmeans_seed): X float64
+    [N, A], the first seed row i0, u float64 [K - 1] in [0, 1) — the j-th further seed is the row
+    at which the running sum of the rows' distances to their nearest seed so far, taken in the
+    contract's order, passes u[j - 1] times its total.  Returns (seeds int32 [K], C float64 [K, A]
+    = X[seeds], w float64 [N]: the distance to the nearest of the K seeds)."""
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("X must be [N, A] with A >= 1")
+    N, A = X.shape
+    K, i0, u = _seed_args(N, K, i0, u)
+    seeds, C, w = np.zeros(K, np.int32), np.zeros((K, A), np.float64), np.zeros(N, np.float64)
+    _lib.check(_lib.lib().dmlp_cpu_kmeans_seed(
+        X.ctypes.data, N, A, K, i0, u.ctypes.data if K > 1 else None, seeds.ctypes.data,
+        C.ctypes.data, w.ctypes.data, nthreads), "cpu kmeans seed")
+    return seeds, C, w
+
+
 # ======================================================================= GPU backend
 def _torch():
     import torch
@@ -1339,6 +1368,28 @@ def cluster_sums_gpu(X, label, K: int, extra=None, *, centroids=None):
                                    _p(ws), nbytes, _p(sums), _p(centroids), _stream()),
                "cluster sums")
     return sums, count
+
+
+def kmeans_seed_gpu(X, K: int, i0: int, u):
+    """kmeans_seed_cpu on the device (dmlp_kmeans_seed, csrc/kmeans_seed.hip): X a float64 [N, A]
+    tensor on a GPU, u a HOST array (checked here, then copied over).  Returns (seeds int32 [K],
+    C float64 [K, A], w float64 [N]) there, the CPU's bits.  2K launches on the current stream,
+    no host sync."""
+    torch = _torch()
+    L = _lib.lib()
+    X = _device_rows(X)
+    N, A = X.shape
+    K, i0, u = _seed_args(N, K, i0, u)
+    dev = X.device
+    ud = torch.from_numpy(u).to(dev)
+    seeds = torch.zeros(K, dtype=torch.int32, device=dev)
+    C = torch.zeros((K, A), dtype=torch.float64, device=dev)
+    w = torch.zeros(N, dtype=torch.float64, device=dev)
+    nbytes = L.dmlp_kmeans_seed_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.dmlp_kmeans_seed(_p(X), N, A, K, i0, _p(ud) if K > 1 else None, _p(seeds), _p(C),
+                                  _p(w), _p(ws), nbytes, _stream()), "kmeans seed")
+    return seeds, C, w
 
 
 # ---------------------------------------------------------------- report text on the GPU

@@ -1,0 +1,144 @@
+#!/usr/bin/env python
+"""The D^2 seeding (csrc/kmeans_seed.hip) on one GPU.  Rows in K Gaussian blobs: K centres uniform
+in [0, 1000)^A, every row a centre plus N(0, 10) noise, drawn on the device from a fixed seed.
+
+  seeding  kmeans_seed_gpu (u copied over, 2K launches, outputs and workspace allocated) against
+           kmeans_seed_cpu on --threads host threads, the same i0 and u; before anything is timed
+           the two are compared (the same seeds, the same bits of C and w).  GPU: device events
+           around a window of back-to-back calls, warmed, median (min .. max) of --reps windows;
+           CPU: a host clock around --cpu-reps calls, the least.
+  update   dmlp_kmeans_seed at K = 1 on buffers made once — one k_seed_update, which reads X once,
+           plus the one-workgroup copy of row i0 — in windows of --inner calls, and Y.copy_(X) on the
+           same X in the same windows, the candidates alternating.  Bytes: N * A * 8 (+ 8 N for
+           w) read by the update, 2 * N * A * 8 moved by the copy.
+  fit      KMeans(K, 0, max_iter=--max-iter, seeding=...) on the same rows, "d2" against
+           "uniform": n_iter_ and inertia_ of one fit each.
+A measurement path that finds no GPU fails.
+
+    python tools/kmeans_seed_bench.py [--n 100000,1000000] [--a 32,128] [--k 64,1024,4096]
+                                      [--reps 5] [--inner 20] [--threads 16] [--json out.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--n", default="100000,1000000")
+    ap.add_argument("--a", default="32,128")
+    ap.add_argument("--k", default="64,1024,4096")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--inner", type=int, default=20, help="calls per timed window of `update`")
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--cpu-reps", type=int, default=1)
+    ap.add_argument("--max-iter", type=int, default=100)
+    ap.add_argument("--no-fit", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args(argv)
+
+    import torch
+    from distributed_machine_learning_project_amd import _lib
+    from distributed_machine_learning_project_amd.models import KMeans
+    from distributed_machine_learning_project_amd.ops import knn as K
+    if not torch.cuda.is_available():
+        raise SystemExit("kmeans_seed_bench needs a GPU")  # no CPU fall-back: its time says nothing
+    L = _lib.lib()
+
+    def window(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def measure(cands, inner):
+        for _ in range(a.warmup):
+            for fn in cands.values():
+                fn()
+        t = {n: [] for n in cands}
+        for _ in range(a.reps):
+            for n, fn in cands.items():
+                t[n].append(window(fn, inner))
+        return {n: {"median": round(statistics.median(v), 4), "min": round(min(v), 4),
+                    "max": round(max(v), 4)} for n, v in t.items()}
+
+    rows = []
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rng = np.random.default_rng(0)
+    for N in (int(s) for s in a.n.split(",")):
+        for A in (int(s) for s in a.a.split(",")):
+            for Kc in (int(s) for s in a.k.split(",")):
+                ctr = 1000.0 * torch.rand((Kc, A), dtype=torch.float64, device="cuda", generator=gen)
+                of = torch.randint(0, Kc, (N,), device="cuda", generator=gen)
+                X = ctr[of] + 10.0 * torch.randn((N, A), dtype=torch.float64, device="cuda",
+                                                 generator=gen)
+                del of
+                Xh = X.cpu().numpy()
+                i0, u = int(rng.integers(N)), rng.random(Kc - 1)
+                row = {"n": N, "a": A, "k": Kc}
+
+                t0 = time.perf_counter()
+                cpu = K.kmeans_seed_cpu(Xh, Kc, i0, u, nthreads=a.threads)
+                cpu_s = [time.perf_counter() - t0]
+                gpu = K.kmeans_seed_gpu(X, Kc, i0, u)
+                assert np.array_equal(gpu[0].cpu().numpy(), cpu[0])
+                assert np.array_equal(gpu[1].cpu().numpy().view(np.int64), cpu[1].view(np.int64))
+                assert np.array_equal(gpu[2].cpu().numpy().view(np.int64), cpu[2].view(np.int64))
+                for _ in range(a.cpu_reps - 1):
+                    t0 = time.perf_counter()
+                    K.kmeans_seed_cpu(Xh, Kc, i0, u, nthreads=a.threads)
+                    cpu_s.append(time.perf_counter() - t0)
+                row["seeding"] = measure({"gpu_ms": lambda: K.kmeans_seed_gpu(X, Kc, i0, u)}, 1)
+                row["seeding"]["cpu_ms"] = round(1e3 * min(cpu_s), 2)
+                row["seeding"]["cpu_threads"] = a.threads
+
+                if Kc == int(a.k.split(",")[0]):    # the update does not depend on K: once per (N, A)
+                    nbytes = L.dmlp_kmeans_seed_bytes(N)
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+                    sd = torch.zeros(1, dtype=torch.int32, device="cuda")
+                    C1 = torch.zeros((1, A), dtype=torch.float64, device="cuda")
+                    w = torch.zeros(N, dtype=torch.float64, device="cuda")
+                    Y = torch.empty_like(X)
+
+                    def update():
+                        _lib.check(L.dmlp_kmeans_seed(X.data_ptr(), N, A, 1, i0, None, sd.data_ptr(),
+                                                      C1.data_ptr(), w.data_ptr(), ws.data_ptr(),
+                                                      nbytes, K._stream()), "kmeans seed")
+                    m = measure({"update_ms": update, "copy_ms": lambda: Y.copy_(X)}, a.inner)
+                    m["update_gbps"] = round((N * A * 8 + N * 8) / m["update_ms"]["median"] / 1e6, 1)
+                    m["copy_gbps"] = round(2 * N * A * 8 / m["copy_ms"]["median"] / 1e6, 1)
+                    row["update"] = m
+                    del Y
+
+                if not a.no_fit:
+                    row["fit"] = {}
+                    for seeding in ("d2", "uniform"):
+                        km = KMeans(Kc, 0, max_iter=a.max_iter, device="gpu", seeding=seeding).fit(Xh)
+                        row["fit"][seeding] = {"n_iter": km.n_iter_, "inertia": km.inertia_}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+
+    out = {"reps": a.reps, "inner": a.inner, "max_iter": a.max_iter,
+           "device": torch.cuda.get_device_name(0), "rows": rows}
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
