@@ -148,6 +148,9 @@ _SIGS = {
     "dmlp_kmeans_seed_bytes": (i64, [i64]),
     "dmlp_kmeans_seed": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "dmlp_cpu_kmeans_seed": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32]),
+    "dmlp_kmeans_seed_trials_bytes": (i64, [i64, i32, i32]),
+    "dmlp_kmeans_seed_trials": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "dmlp_cpu_kmeans_seed_trials": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32]),
     "dmlp_merge": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]),
     "dmlp_finalize": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
     "dmlp_vote_curve_kmax": (i32, []),

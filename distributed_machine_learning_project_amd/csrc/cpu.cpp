@@ -383,59 +383,102 @@ int64_t seed_walk(int64_t n, Val val, double& s, double t) {
 
 }  // namespace
 
-// dmlp_kmeans_seed on the host: the update threaded over the runs of 64 rows, the block sums, the
-// total and the walk serial, the same operations in the same order.
+// The seeding with L local trials per step (dmlp.h "k-means seeding, local trials"); L = 1 is
+// dmlp_kmeans_seed's contract.  A trial step is threaded over the runs of 64 rows: a row is read
+// once for all L candidates, its w_i taken from the row of m that won the step before and its L
+// minima written in place (m[0] is the caller's w, rows 1 .. L - 1 are allocated here).  The block
+// sums, the totals and the walks are serial, the same operations in the same order.
+namespace {
+
+int seed_trials(const double* X, int64_t N, int A, int K, int L, int i0, const double* u,
+                int* seeds, double* C, double* w, int nthreads) {
+  const int64_t nruns = (N + 63) / 64, nblocks = (nruns + 63) / 64;
+  std::vector<double> more((size_t)(L - 1) * N), R((size_t)L * nruns), B((size_t)L * nblocks);
+  std::vector<double*> m((size_t)L);
+  for (int l = 0; l < L; ++l) m[l] = l ? more.data() + (int64_t)(l - 1) * N : w;
+  std::vector<int64_t> cand((size_t)L, i0);
+  const int nt = default_threads(nthreads);
+  const double* cur = nullptr;   // the winning trial's m: w for the rows so far (step 0: +inf)
+  int best = 0;
+  // live trials of the candidates against cur, then the winner: the smallest l with the least P_l
+  auto trials = [&](int live) {
+    parallel_for(nruns, nt, [&](int64_t r) {
+      double s[16];
+      for (int l = 0; l < live; ++l) s[l] = 0.0;
+      for (int64_t i = r * 64; i < std::min(N, r * 64 + 64); ++i) {
+        const double wi = cur ? cur[i] : INFINITY;
+        for (int l = 0; l < live; ++l) {
+          const double d = exact_dist(X + i * A, X + cand[l] * A, A);
+          const double ml = d < wi ? d : wi;
+          m[l][i] = ml;
+          s[l] = s[l] + (ml < INFINITY ? ml : 0.0);
+        }
+      }
+      for (int l = 0; l < live; ++l) R[l * nruns + r] = s[l];
+    });
+    double P = 0.0;
+    for (int l = 0; l < live; ++l) {
+      double T = 0.0;
+      for (int64_t b = 0; b < nblocks; ++b) {
+        double s = 0.0;
+        for (int64_t r = b * 64; r < std::min(nruns, b * 64 + 64); ++r) s = s + R[l * nruns + r];
+        B[l * nblocks + b] = s;
+        T = T + s;
+      }
+      if (l == 0 || T < P) {
+        P = T;
+        best = l;
+      }
+    }
+    cur = m[best];
+    return P;
+  };
+  for (int j = 0; j < K; ++j) {
+    const double T = trials(j ? L : 1);
+    seeds[j] = (int)cand[best];
+    std::memcpy(C + (int64_t)j * A, X + cand[best] * A, sizeof(double) * A);
+    if (j == K - 1) break;
+    const double *Bc = B.data() + best * nblocks, *Rc = R.data() + best * nruns;
+    for (int l = 0; l < L; ++l) {
+      const double ul = u[(int64_t)j * L + l];
+      if (!(T > 0.0 && T < INFINITY)) {
+        const double p = ul * (double)N;
+        cand[l] = p >= 0.0 ? (p < (double)N ? (int64_t)p : N - 1) : 0;   // (a NaN u: row 0)
+        continue;
+      }
+      const double t = ul * T;
+      double s = 0.0;
+      const int64_t b = seed_walk(nblocks, [&](int64_t i) { return Bc[i]; }, s, t);
+      const int64_t r = b * 64 + seed_walk(std::min<int64_t>(64, nruns - b * 64),
+                                           [&](int64_t i) { return Rc[b * 64 + i]; }, s, t);
+      cand[l] = r * 64 + seed_walk(std::min<int64_t>(64, N - r * 64), [&](int64_t i) {
+                  const double wi = cur[r * 64 + i];
+                  return wi < INFINITY ? wi : 0.0; }, s, t);
+    }
+  }
+  if (cur != w) std::memcpy(w, cur, sizeof(double) * N);
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int dmlp_cpu_kmeans_seed(const double* X, int64_t N, int A, int K, int i0,
                                     const double* u, int* seeds, double* C, double* w,
                                     int nthreads) {
   if (N <= 0 || K <= 0) return 0;
   if (N > INT32_MAX || A < 1 || i0 < 0 || i0 >= N || !X || (K > 1 && !u) || !seeds || !C || !w)
     return -1;
-  const int64_t nruns = (N + 63) / 64, nblocks = (nruns + 63) / 64;
-  std::vector<double> R((size_t)nruns), B((size_t)nblocks);
-  const int nt = default_threads(nthreads);
-  for (int64_t i = 0; i < N; ++i) w[i] = INFINITY;
-  auto update = [&](const double* c) {
-    parallel_for(nruns, nt, [&](int64_t r) {
-      double s = 0.0;
-      for (int64_t i = r * 64; i < std::min(N, r * 64 + 64); ++i) {
-        const double d = exact_dist(X + i * A, c, A);
-        w[i] = d < w[i] ? d : w[i];
-        s = s + (w[i] < INFINITY ? w[i] : 0.0);
-      }
-      R[r] = s;
-    });
-  };
-  auto take = [&](int j, int64_t row) {
-    seeds[j] = (int)row;
-    std::memcpy(C + (int64_t)j * A, X + row * A, sizeof(double) * A);
-  };
-  take(0, i0);
-  for (int j = 1; j < K; ++j) {
-    update(C + (int64_t)(j - 1) * A);
-    double T = 0.0;
-    for (int64_t b = 0; b < nblocks; ++b) {
-      double s = 0.0;
-      for (int64_t r = b * 64; r < std::min(nruns, b * 64 + 64); ++r) s = s + R[r];
-      B[b] = s;
-      T = T + s;
-    }
-    if (!(T > 0.0 && T < INFINITY)) {
-      const double p = u[j - 1] * (double)N;
-      take(j, p >= 0.0 ? (p < (double)N ? (int64_t)p : N - 1) : 0);   // (a NaN u: row 0)
-      continue;
-    }
-    const double t = u[j - 1] * T;
-    double s = 0.0;
-    const int64_t b = seed_walk(nblocks, [&](int64_t i) { return B[i]; }, s, t);
-    const int64_t r = b * 64 + seed_walk(std::min<int64_t>(64, nruns - b * 64),
-                                         [&](int64_t i) { return R[b * 64 + i]; }, s, t);
-    take(j, r * 64 + seed_walk(std::min<int64_t>(64, N - r * 64), [&](int64_t i) {
-           const double wi = w[r * 64 + i];
-           return wi < INFINITY ? wi : 0.0; }, s, t));
-  }
-  update(C + (int64_t)(K - 1) * A);
-  return 0;
+  return seed_trials(X, N, A, K, 1, i0, u, seeds, C, w, nthreads);
+}
+
+extern "C" int dmlp_cpu_kmeans_seed_trials(const double* X, int64_t N, int A, int K, int L, int i0,
+                                           const double* u, int* seeds, double* C, double* w,
+                                           int nthreads) {
+  if (N <= 0 || K <= 0) return 0;
+  if (N > INT32_MAX || A < 1 || L < 1 || L > 16 || i0 < 0 || i0 >= N || !X || (K > 1 && !u) ||
+      !seeds || !C || !w)
+    return -1;
+  return seed_trials(X, N, A, K, L, i0, u, seeds, C, w, nthreads);
 }
 
 extern "C" int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk,

@@ -633,6 +633,42 @@ int dmlp_kmeans_seed(const double* X, int64_t N, int A, int K, int i0, const dou
                      int* seeds /*[K]*/, double* C /*[K][A]*/, double* w /*[N]*/, void* ws,
                      int64_t ws_bytes, void* stream);
 
+// ---------------------------------------------------------------- device: k-means seeding, local trials (kmeans_seed.hip)
+// Greedy k-means++: every step draws L candidates from the D^2 distribution and keeps the one that
+// lowers the potential the most.  The same words for dmlp_kmeans_seed_trials and
+// dmlp_cpu_kmeans_seed_trials: a pure function of its inputs, bit-identical on both devices.
+// Takes rows X [N][A], K >= 1, a trial count L with 1 <= L <= 16, a first row id i0 in [0, N) and
+// u [K - 1][L] doubles with 0 <= u < 1, row-major (in device memory for the device entry; not
+// read, and nullable, at K = 1).  Writes seeds, C and w as dmlp_kmeans_seed defines them.
+// A TRIAL of candidate row p against the current w: d_i = d(x_i, x_p), the contract's distance
+// (left to right, sub, mul and add each rounded, no FMA); m_i = d_i < w_i ? d_i : w_i, so a NaN d
+// leaves w_i; v_i = m_i < +inf ? m_i : 0.0; P = the fixed-order sum of v — the section above's
+// R_r (runs of 64 rows), B_b (blocks of 64 runs) and T (the blocks left to right), each from 0.0.
+//   Step 0.  seeds[0] = i0; w becomes the m of the trial of i0 against w = +inf, and that trial's
+//     sums are the current R, B and T.
+//   Step j = 1 .. K - 1.  For l = 0 .. L - 1 candidate p_l is picked from the current w, R, B and
+//     T with u[j - 1][l] by step 3 of the section above, unchanged (the degenerate case
+//     (int)(u * N) when not 0 < T < +inf, the fallbacks, the clamp into [0, N), row 0 for a NaN
+//     product).  Candidates may coincide.  Each is trialled against the same w: m^l and P_l.
+//     l* is the SMALLEST l with the least P_l (a strict < in ascending l; P is never NaN, every
+//     term being >= +0.0 and finite, but may be +inf).  seeds[j] = p_l*, w = m^l*, and the current
+//     R, B and T are those of trial l*: the next pick needs no new sums, and after the last step
+//     w belongs to all K seeds.
+// With L = 1 this is dmlp_kmeans_seed's result bit for bit in seeds, C and w.
+// 2K + 2 launches on the caller's stream, no host sync: per step one workgroup that takes the
+// winner of the step before and picks the candidates, then one pass over X for all L trials;
+// after the last step the winner once more and w = m^l*, the only copy over N.
+// ws: dmlp_kmeans_seed_trials_bytes(N, A, L) bytes — m [L][N], R [L][ceil(N / 64)], B [L][ceil(N
+// / 4096)], the candidate rows [L][A] and 1 + L state words (-1 for N < 0, N > INT_MAX, A < 1 or
+// L outside [1, 16]).
+// N <= 0 or K <= 0 returns 0, launches nothing and writes nothing.  N > INT_MAX, A < 1, L outside
+// [1, 16], i0 outside [0, N), a null pointer (u at K = 1 excepted) or a workspace smaller than
+// advertised return -1 before any launch; a launch failure returns -(int)hipError.
+int64_t dmlp_kmeans_seed_trials_bytes(int64_t N, int A, int L);
+int dmlp_kmeans_seed_trials(const double* X, int64_t N, int A, int K, int L, int i0,
+                            const double* u /*[K-1][L]*/, int* seeds /*[K]*/, double* C /*[K][A]*/,
+                            double* w /*[N]*/, void* ws, int64_t ws_bytes, void* stream);
+
 // ---------------------------------------------------------------- device: k-means, screened (kmeans_screen.hip)
 // A second way to dmlp_kmeans_assign's label, dmin and *changed, bit for bit: a single-term bf16
 // MFMA screen with dmlp_screen_x1_bound2(A, 2)'s bound keeps the centroids whose score is within
@@ -846,6 +882,11 @@ int dmlp_cpu_cluster_sums(const double* X, int64_t N, int A, int K, const double
 // over the runs, the sums and the walk serial; the same bits, the same argument checks.
 int dmlp_cpu_kmeans_seed(const double* X, int64_t N, int A, int K, int i0, const double* u,
                          int* seeds, double* C, double* w, int nthreads);
+// dmlp_kmeans_seed_trials' contract on the host (u in host memory, no workspace; (L - 1) * N
+// doubles are allocated): the trials threaded over the runs, a row read once for all L; L = 1 is
+// dmlp_cpu_kmeans_seed's loop.
+int dmlp_cpu_kmeans_seed_trials(const double* X, int64_t N, int A, int K, int L, int i0,
+                                const double* u, int* seeds, double* C, double* w, int nthreads);
 int dmlp_cpu_finalize(const double* d, const int* ids, int kstride, const int* qk, int64_t Q,
                       const int* labels, int* out_label, uint64_t* out_cs);
 int dmlp_cpu_merge(const double* in_d, const int* in_i, int L, int64_t list_stride, int kin,

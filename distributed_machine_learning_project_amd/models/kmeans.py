@@ -29,7 +29,14 @@ picked there without a host sync.  The spelling is a keyword of its own because 
 "k-means++" has always been a ValueError here and stays one; seeding="uniform" (the default) is
 the draw of K distinct rows, as before.
 
-Not offered yet: greedy k-means++ (local trials), n_init restarts, sample_weight, a multi-rank
+seeding="greedy" is greedy k-means++ (dmlp.h "k-means seeding, local trials"): every step draws
+L = n_local_trials candidates that way (None: 2 + int(ln K); an int in 1 .. 16) and keeps the one
+that leaves the least sum of the rows' distances to their nearest seed, the first of equals.  The
+draws: rng as above, i0 = int(rng.integers(N)), u = rng.random((K - 1, L)); with L = 1 this is
+"d2", draw for draw and bit for bit.  On a GPU one pass over X per step serves all L trials
+(k_seed_trial, csrc/kmeans_seed.hip), again without a host sync.
+
+Not offered yet: n_init restarts, sample_weight, a multi-rank
 front end, a 3-term (hi/lo) screen for tightly packed centroids, the screen at A > 128.
 """
 from __future__ import annotations
@@ -93,21 +100,30 @@ def _rows(X, name: str = "X", A=None):
 
 class KMeans:
     def __init__(self, n_clusters: int, init, max_iter: int = 300, tol: float = 0.0,
-                 device: str = "auto", assign: str = "auto", seeding: str = "uniform"):
+                 device: str = "auto", assign: str = "auto", seeding: str = "uniform",
+                 n_local_trials=None):
         """init: a [K, A] array of centroids, "first" (rows 0 .. K - 1 of X), or an int seed (K
         distinct rows of X drawn by numpy.random.default_rng(seed).choice, taken in ascending row
         id).  seeding="d2", with an int seed only: D^2 (k-means++) seeding from that generator;
-        seed_rows_ then holds the K seed rows."""
+        seed_rows_ then holds the K seed rows.  seeding="greedy", likewise: n_local_trials
+        candidates per step (None: 2 + int(ln K); else an int in 1 .. 16), the best one kept."""
         for v, name in ((n_clusters, "n_clusters"), (max_iter, "max_iter")):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1")
         if not float(tol) >= 0.0:
             raise ValueError("tol must be >= 0")
         self.n_clusters, self.max_iter, self.tol = int(n_clusters), int(max_iter), float(tol)
-        if seeding not in ("uniform", "d2"):
-            raise ValueError('seeding must be "uniform" or "d2"')
-        if seeding == "d2" and not self._is_seed(init):
-            raise ValueError('seeding="d2" needs init=<int seed>')
+        if seeding not in ("uniform", "d2", "greedy"):
+            raise ValueError('seeding must be "uniform", "d2" or "greedy"')
+        if seeding != "uniform" and not self._is_seed(init):
+            raise ValueError(f'seeding="{seeding}" needs init=<int seed>')
+        if n_local_trials is not None and (seeding != "greedy" or not self._is_seed(n_local_trials)
+                                           or not 1 <= n_local_trials <= 16):
+            raise ValueError('n_local_trials: an int in 1 .. 16, with seeding="greedy" only')
+        if seeding == "greedy":
+            # None: scikit-learn's count, within 1 .. 16 for any K an int32 holds
+            self.n_local_trials = int(n_local_trials) if n_local_trials is not None else \
+                2 + int(np.log(self.n_clusters))
         self.init, self.seeding = init, seeding
         self._ops = _Ops(device, assign)
         self.on_gpu = self._ops.on_gpu
@@ -117,13 +133,14 @@ class KMeans:
         return isinstance(init, (int, np.integer)) and not isinstance(init, bool)
 
     def _seed_d2(self, Xd):
-        """(seeds, C) where Xd lies: the D^2 seeding of the rows from init's generator"""
+        """(seeds, C) where Xd lies: the D^2 seeding of the rows from init's generator, greedy
+        with a 2-D u"""
         N, Kc = Xd.shape[0], self.n_clusters
         if N < Kc:
             raise ValueError(f"{N} rows cannot seed {Kc} clusters")
         rng = np.random.default_rng(int(self.init))
         i0 = int(rng.integers(N))
-        u = rng.random(Kc - 1)
+        u = rng.random(Kc - 1 if self.seeding == "d2" else (Kc - 1, self.n_local_trials))
         seed = K.kmeans_seed_gpu if self.on_gpu else K.kmeans_seed_cpu
         return seed(Xd, Kc, i0, u)[:2]
 
@@ -148,7 +165,7 @@ class KMeans:
         if not X.shape[0]:
             raise ValueError("X has no rows")
         o, Kc, A = self._ops, self.n_clusters, X.shape[1]
-        if self.seeding == "d2":
+        if self.seeding != "uniform":
             Xd = o.put(X)                   # the rows go over first: the seeds are picked there
             seeds, C = self._seed_d2(Xd)    # C is updated in place by the Lloyd step
             self.seed_rows_ = o.get(seeds)

@@ -514,31 +514,45 @@ def cluster_sums_cpu(X, label, K: int, extra=None, *, centroids=None, nthreads: 
 
 
 def _seed_args(N: int, K, i0, u):
-    """(K, i0, u float64 [K - 1]) of a D^2 seeding over N rows, checked on the host"""
+    """(K, i0, u float64 [K - 1] or [K - 1, L], L or None for a 1-D u) of a D^2 seeding over N
+    rows, checked on the host"""
     K, i0 = int(K), int(i0)
     u = np.ascontiguousarray(u, np.float64)
     if K < 1 or not 0 <= i0 < N:
         raise ValueError("K must be >= 1 and i0 a row id in [0, N)")
-    if u.shape != (K - 1,) or not ((u >= 0.0) & (u < 1.0)).all():
+    L = u.shape[1] if u.ndim == 2 else None
+    if L is None and u.shape != (K - 1,):
         raise ValueError("u must be [K - 1] with 0 <= u < 1")
-    return K, i0, u
+    if L is not None and (u.shape[0] != K - 1 or not 1 <= L <= 16):
+        raise ValueError("a 2-D u must be [K - 1, L] with 1 <= L <= 16")
+    if not ((u >= 0.0) & (u < 1.0)).all():
+        raise ValueError("u must hold 0 <= u < 1")
+    return K, i0, u, L
 
 
 def kmeans_seed_cpu(X, K: int, i0: int, u, nthreads: int = 0):
     """D^2 (k-means++) seeding by dmlp.h's fixed-order contract (dmlp_cpu_kmeans_seed): X float64
     [N, A], the first seed row i0, u float64 [K - 1] in [0, 1) — the j-th further seed is the row
     at which the running sum of the rows' distances to their nearest seed so far, taken in the
-    contract's order, passes u[j - 1] times its total.  Returns (seeds int32 [K], C float64 [K, A]
-    = X[seeds], w float64 [N]: the distance to the nearest of the K seeds)."""
+    contract's order, passes u[j - 1] times its total.  A 2-D u [K - 1, L], 1 <= L <= 16, is the
+    greedy variant (dmlp_cpu_kmeans_seed_trials, dmlp.h "k-means seeding, local trials"): L rows
+    are drawn that way per step with u[j - 1][:], and the one that leaves the least sum of
+    distances is kept, the first of equals.  Returns (seeds int32 [K], C float64 [K, A] =
+    X[seeds], w float64 [N]: the distance to the nearest of the K seeds)."""
     X = np.ascontiguousarray(X, np.float64)
     if X.ndim != 2 or X.shape[1] < 1:
         raise ValueError("X must be [N, A] with A >= 1")
     N, A = X.shape
-    K, i0, u = _seed_args(N, K, i0, u)
+    K, i0, u, L = _seed_args(N, K, i0, u)
     seeds, C, w = np.zeros(K, np.int32), np.zeros((K, A), np.float64), np.zeros(N, np.float64)
-    _lib.check(_lib.lib().dmlp_cpu_kmeans_seed(
-        X.ctypes.data, N, A, K, i0, u.ctypes.data if K > 1 else None, seeds.ctypes.data,
-        C.ctypes.data, w.ctypes.data, nthreads), "cpu kmeans seed")
+    up = u.ctypes.data if K > 1 else None
+    out = (seeds.ctypes.data, C.ctypes.data, w.ctypes.data, nthreads)
+    if L is None:
+        _lib.check(_lib.lib().dmlp_cpu_kmeans_seed(X.ctypes.data, N, A, K, i0, up, *out),
+                   "cpu kmeans seed")
+    else:
+        _lib.check(_lib.lib().dmlp_cpu_kmeans_seed_trials(X.ctypes.data, N, A, K, L, i0, up, *out),
+                   "cpu kmeans seed trials")
     return seeds, C, w
 
 
@@ -1374,21 +1388,27 @@ def kmeans_seed_gpu(X, K: int, i0: int, u):
     """kmeans_seed_cpu on the device (dmlp_kmeans_seed, csrc/kmeans_seed.hip): X a float64 [N, A]
     tensor on a GPU, u a HOST array (checked here, then copied over).  Returns (seeds int32 [K],
     C float64 [K, A], w float64 [N]) there, the CPU's bits.  2K launches on the current stream,
-    no host sync."""
+    no host sync.  A 2-D u [K - 1, L] is the greedy variant (dmlp_kmeans_seed_trials): one pass
+    over X per step for all L trials, 2K + 2 launches, a workspace of L * N doubles."""
     torch = _torch()
     L = _lib.lib()
     X = _device_rows(X)
     N, A = X.shape
-    K, i0, u = _seed_args(N, K, i0, u)
+    K, i0, u, nl = _seed_args(N, K, i0, u)
     dev = X.device
     ud = torch.from_numpy(u).to(dev)
     seeds = torch.zeros(K, dtype=torch.int32, device=dev)
     C = torch.zeros((K, A), dtype=torch.float64, device=dev)
     w = torch.zeros(N, dtype=torch.float64, device=dev)
-    nbytes = L.dmlp_kmeans_seed_bytes(N)
+    nbytes = L.dmlp_kmeans_seed_bytes(N) if nl is None else L.dmlp_kmeans_seed_trials_bytes(N, A, nl)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _lib.check(L.dmlp_kmeans_seed(_p(X), N, A, K, i0, _p(ud) if K > 1 else None, _p(seeds), _p(C),
-                                  _p(w), _p(ws), nbytes, _stream()), "kmeans seed")
+    up = _p(ud) if K > 1 else None
+    if nl is None:
+        _lib.check(L.dmlp_kmeans_seed(_p(X), N, A, K, i0, up, _p(seeds), _p(C), _p(w), _p(ws),
+                                      nbytes, _stream()), "kmeans seed")
+    else:
+        _lib.check(L.dmlp_kmeans_seed_trials(_p(X), N, A, K, nl, i0, up, _p(seeds), _p(C), _p(w),
+                                             _p(ws), nbytes, _stream()), "kmeans seed trials")
     return seeds, C, w
 
 

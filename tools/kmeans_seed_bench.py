@@ -11,12 +11,17 @@ in [0, 1000)^A, every row a centre plus N(0, 10) noise, drawn on the device from
            plus the one-workgroup copy of row i0 — in windows of --inner calls, and Y.copy_(X) on the
            same X in the same windows, the candidates alternating.  Bytes: N * A * 8 (+ 8 N for
            w) read by the update, 2 * N * A * 8 moved by the copy.
-  fit      KMeans(K, 0, max_iter=--max-iter, seeding=...) on the same rows, "d2" against
-           "uniform": n_iter_ and inertia_ of one fit each.
+  trials   (--trials L,...) the greedy seeding, kmeans_seed_gpu with u [K - 1, L], for every L
+           beside the D^2 seeding (the 1-D u) on the same rows and i0: one call per window, the
+           candidates alternating; per step = median / K.  At the first K of --k every L is first
+           compared with the host twin (the same seeds, the same bits of C and w).
+  fit      KMeans(K, 0, max_iter=--max-iter, seeding=...) on the same rows, "d2" and "greedy"
+           (its default trial count) against "uniform": n_iter_ and inertia_ of one fit each.
 A measurement path that finds no GPU fails.
 
     python tools/kmeans_seed_bench.py [--n 100000,1000000] [--a 32,128] [--k 64,1024,4096]
-                                      [--reps 5] [--inner 20] [--threads 16] [--json out.json]
+                                      [--trials 1,4,8] [--reps 5] [--inner 20] [--threads 16]
+                                      [--json out.json]
 """
 import argparse
 import json
@@ -41,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--cpu-reps", type=int, default=1)
     ap.add_argument("--max-iter", type=int, default=100)
+    ap.add_argument("--trials", default="", help="trial counts of the greedy seeding, e.g. 1,4,8")
     ap.add_argument("--no-fit", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
@@ -122,9 +128,25 @@ def main(argv=None):
                     row["update"] = m
                     del Y
 
+                if a.trials:
+                    cands = {"d2": lambda: K.kmeans_seed_gpu(X, Kc, i0, u)}
+                    for nl in (int(s) for s in a.trials.split(",")):
+                        ul = rng.random((Kc - 1, nl))
+                        if Kc == int(a.k.split(",")[0]):
+                            got = K.kmeans_seed_gpu(X, Kc, i0, ul)
+                            ref = K.kmeans_seed_cpu(Xh, Kc, i0, ul, nthreads=a.threads)
+                            assert np.array_equal(got[0].cpu().numpy(), ref[0])
+                            for g, r in zip(got[1:], ref[1:]):
+                                assert np.array_equal(g.cpu().numpy().view(np.int64),
+                                                      r.view(np.int64))
+                        cands[f"l{nl}"] = lambda ul=ul: K.kmeans_seed_gpu(X, Kc, i0, ul)
+                    row["trials"] = measure(cands, 1)
+                    for m in row["trials"].values():
+                        m["per_step_us"] = round(1e3 * m["median"] / Kc, 1)
+
                 if not a.no_fit:
                     row["fit"] = {}
-                    for seeding in ("d2", "uniform"):
+                    for seeding in ("d2", "greedy", "uniform"):
                         km = KMeans(Kc, 0, max_iter=a.max_iter, device="gpu", seeding=seeding).fit(Xh)
                         row["fit"][seeding] = {"n_iter": km.n_iter_, "inertia": km.inertia_}
                 rows.append(row)
